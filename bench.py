@@ -8,14 +8,21 @@ summed over ranks with an RCCL all-reduce — the only collective; the codeword 
 data-path exchange, so scaling is weak).
 
     python bench.py [--gpus N --steps K --warmup W]                  # N ranks, one GPU each (started here)
+    python bench.py --full ...                                       # plus every secondary measurement (below)
     torchrun --nproc-per-node N ... bench.py --gpus N ...            # the same under a launcher
 
 --gpus N is authoritative: without launcher variables, N > 1 starts N fresh rank processes of this script
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, RCCL) before this process touches a GPU, streams rank 0's
 line and exits with the worst rank's code; under a launcher, WORLD_SIZE must equal N.
 
-The other BASELINE.json configs run as short legs of the same script after the headline, reported under
-``side.configs`` (never ``value``), each event-timed over LEGS[...]['passes'] launches per Eb/N0 point with its own
+A plain run does only what the headline needs: set-up, the BER pass, the warmup, the K timed steps, the result
+line.  ``--dump-outputs DIR`` also writes what the last timed step decoded (DIR/bits.npy, float32 0/1; a fixed
+seeded sample of the batch's rows above DUMP_BYTES) so that two builds can be compared output for output.
+
+``--full`` adds the secondary measurements (never ``value``): the CPU baselines (``cpu_baseline``), the drop-in and
+tanh-SP side numbers (``side``, ``dropin_cw_per_s``) and the other BASELINE.json configs, which run as short legs
+of the same script after the headline, reported under
+``side.configs``, each event-timed over LEGS[...]['passes'] launches per Eb/N0 point with its own
 roofline from profiles/counters.json: configs[2] (1944,5/6) tanh-SP 50 it on 16-QAM OFDM LLRs, B=32,768;
 configs[3] (1296,2/3) 5-bit min-sum <=20 it early stop, B=65,536; configs[4] DVB-S2 64800 rate 1/2 min-sum
 50 it, B=4,096 per GPU.  Under torchrun (N>1) the config [4] leg runs on every rank — the BASELINE
@@ -77,6 +84,11 @@ def main():
     ap.add_argument("--qstep", type=float, default=1.0, help="qminsum: LLR quantisation step (5-bit: qmax 15)")
     ap.add_argument("--mod", default="bpsk", choices=["bpsk", "qpsk-ofdm", "16qam-ofdm"],
                     help="LLR generator (outside the timed region): BPSK/AWGN or the OFDM front end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's decoded bits to DIR/bits.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: CPU baselines, decode_bits / tanh-SP side numbers, "
+                         "the BASELINE configs[2..4] legs (each can be left out with its --no-* switch)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline sample time")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true", help="skip the decode_bits / tanh-SP side measurements")
@@ -125,6 +137,8 @@ def main():
     wl = Workload(args, rank, local)
     pending = wl.ber_launch()           # untimed BER pass over every point, queued: the warmup follows it directly
     elapsed, my_elapsed, gpu_ms = wl.timed(args.steps, args.warmup, world)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "bits" if world == 1 else f"bits_rank{rank}", wl.bits, args.seed)
     ber = wl.ber_finish(pending)
     B, n, E = wl.B, wl.n, wl.E
     total_cw = world * args.steps * B
@@ -132,11 +146,12 @@ def main():
     value = total_cw / elapsed
     roof = roofline(n, E, B, gpu_ms, args, wl.kpath, wl.m, wl.mean_iters, clock=wl.clock)
 
+    # everything below the headline runs under --full only
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # CPU baseline at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # CPU baseline at N=1 only
         cpu = cpu_baseline(wl.H, args, wl.rate)
     side = {}
-    if rank == 0 and world == 1 and not args.no_dropin and B * n * 8 <= (1 << 32):
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and B * n * 8 <= (1 << 32):
         side = side_measurements(wl.H, wl.dec, wl.llrs, B, args, wl.kpath)
         ref = reference_cpu(args)
         if cpu is not None and ref is not None:
@@ -149,7 +164,7 @@ def main():
     # BASELINE.json configs[2..4] (never `value`): at N=1 all three on this GPU; at N>1 config [4] (the
     # DVB-S2 multi-GPU config) on every rank, its counters reduced by the same all-reduce
     legs = (list(LEGS) if world == 1 else ["config4"]) if args.legs == "auto" else [x for x in args.legs.split(",") if x]
-    legs = [] if args.no_legs else legs
+    legs = [] if args.no_legs or not args.full else legs
     for x in legs:
         if x not in LEGS:
             raise SystemExit(f"unknown leg {x!r}; choose from {sorted(LEGS)}")
@@ -399,6 +414,23 @@ class Workload:
     def free(self):
         self.llrs = []
         self.cw = self.ws = self.bits = None
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs: the most one array takes on disk
+
+
+def dump_outputs(dirname, name, bits, seed):
+    """``dirname/name.npy``: the decoded bits the last timed step left in the output buffer, float32 0/1 [rows, n].
+    A batch above DUMP_BYTES is sampled: rows drawn once from --seed (sorted, without replacement), so that the same
+    arguments give the same rows on every build."""
+    B, n = bits.shape
+    rows = DUMP_BYTES // (4 * n)
+    if B > rows:
+        import torch
+        idx = np.sort(np.random.default_rng(seed).choice(B, size=rows, replace=False))
+        bits = bits[torch.from_numpy(idx).to(bits.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), bits.cpu().numpy().astype(np.float32))
 
 
 def library_env():

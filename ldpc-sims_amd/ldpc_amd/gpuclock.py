@@ -134,4 +134,6 @@ class ClockSampler:
             out["note"] = "power and residency are firmware averages; meaningful over windows of >= ~0.3 s"
         if self.err is not None:
             out["error"] = self.err
+        elif not s:  # a loop shorter than the poll period: say so, like every other reason for no reading
+            out["error"] = "no sample fell inside the timed loop (shorter than the poll period)"
         return out

@@ -7,7 +7,7 @@ LDPC_PARITY_LOG=$PWD/$OUT/soft_parity.jsonl timeout -k 10 900 python -u -m pytes
 tail -2 $OUT/pytest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 || { tail -10 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -10 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -10 $OUT/bench.err; exit 1; }
 python -c "
 import json; d=json.load(open('$OUT/bench.json'))
 print('headline', round(d['value']/1e6,2), 'M', d['ms_per_step'], 'ms', 'roofline', d['roofline']['bound'], round(d['roofline']['frac'],3))

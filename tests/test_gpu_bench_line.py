@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "8192",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--batch", "8192",
                           "--cpu-seconds", "0.5", "--leg-batch-scale", "0.0625"], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -69,3 +69,35 @@ def test_bench_line_contract():
             assert r["clock_mhz"] == clk["clock_mhz"]
             assert abs(r["frac_at_clock"] - r["frac"] * 2400.0 / clk["clock_mhz"]) < 1e-9
     assert d["ranks"]["per_rank"][0]["clock"] == clk
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline only (no CPU baseline, side numbers or legs), --steps is the
+    number of timed steps, and --dump-outputs writes the last timed step's bits: float32 0/1, the same from run to
+    run, and codewords wherever the BER pass over the same LLRs counted no block error."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "ldpc-sims_amd"))
+    import ldpc_amd
+
+    def run(d):
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8192",
+                              "--ebn0", "1.5:0.5:1.5", "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True,
+                             timeout=120)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        assert os.listdir(d) == ["bits.npy"]
+        return json.loads(lines[0]), np.load(os.path.join(d, "bits.npy"))
+
+    d, bits = run(tmp_path / "a")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 8192 / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    assert d["cpu_baseline"] is None and d["side"] is None and d["dropin_cw_per_s"] is None
+    assert d["roofline"]["frac"] > 0 and len(d["ber"]["ebn0_db"]) == 1
+    assert bits.dtype == np.float32 and bits.shape == (8192, 648) and set(np.unique(bits)) <= {0.0, 1.0}
+    H, _ = ldpc_amd.get_code("wifi648_12")
+    ok = ((bits.astype(np.int64) @ np.asarray(H, dtype=np.int64).T) % 2 == 0).all(axis=1).mean()
+    bler = d["ber"]["coded_bler"][0]
+    assert 0 < bler < 1 and 1 - bler <= ok < 1   # 1.5 dB: about a third of the blocks fail, so the bound bites
+    _, again = run(tmp_path / "b")
+    assert np.array_equal(bits, again)

@@ -131,11 +131,11 @@ def test_bench_dvbs2_config4_two_ranks_equal_one_process():
 
 
 def test_bench_multigpu_runs_the_config4_leg():
-    """At N>1 bench.py also runs BASELINE config [4] (DVB-S2 64800 rate 1/2, 50 min-sum iterations) on every
+    """At N>1 bench.py --full also runs BASELINE config [4] (DVB-S2 64800 rate 1/2, 50 min-sum iterations) on every
     rank — the multi-GPU configuration BASELINE names — under side.configs.config4, with max-over-ranks
     timing, every rank's timed seconds in its ``ranks`` and the counters summed by the all-reduce: equal to
     one process decoding both shards (here 256 codewords per rank through --leg-batch-scale)."""
-    common = ["bench.py", "--steps", "1", "--warmup", "0", "--iters", "5", "--batch", "1024", "--ebn0", "1:1:2",
+    common = ["bench.py", "--full", "--steps", "1", "--warmup", "0", "--iters", "5", "--batch", "1024", "--ebn0", "1:1:2",
               "--no-cpu-baseline", "--no-dropin"]
     two = _bench_line(_launch([*common, "--gpus", "2", "--leg-batch-scale", "0.0625"], 2, timeout=400))
     one = _bench_line(_launch([*common, "--gpus", "1", "--legs", "config4", "--leg-batch-scale", "0.125"], 1,

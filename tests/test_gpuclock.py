@@ -33,3 +33,10 @@ def test_summary_without_accumulators_or_amdsmi():
     assert s["clock_mhz"] == 2000.0 and "socket_power_w" not in s and "limit_residency" not in s
     e = _sampler([], None, None, err="ModuleNotFoundError: amdsmi").summary()
     assert e["error"].startswith("ModuleNotFoundError") and "clock_mhz" not in e
+
+
+def test_summary_loop_shorter_than_poll_period():
+    """A timed loop that ends before the first poll after its start has no sample of its own: the record says why
+    there is no clock rather than carrying neither a clock nor a reason."""
+    s = _sampler([(0.999, 2000.0, 2000, None)], None, None).summary(since=1.0)
+    assert s["samples"] == 0 and "clock_mhz" not in s and "poll period" in s["error"]
