@@ -42,8 +42,32 @@ enum {
     LDPC_F_DEVICE_PTRS = 2,   /* llr/bits/soft/iters_used are device pointers (else host)     */
     LDPC_F_F64 = 4,           /* tanh-SP in float64: llr/soft are double* (reference .double()) */
     LDPC_F_SOFT_Z = 8,        /* soft_out = z = 0.5*(L + sum c2v) (half posterior LLR, P0/P1)  */
-    LDPC_F_FORCE_GENERIC = 16 /* never use a structure-specialised (QC) kernel                 */
+    LDPC_F_FORCE_GENERIC = 16,/* never use a structure-specialised (QC) kernel                 */
+    LDPC_F_LAYERED = 32       /* layered (row-serial) schedule instead of flooding, see below  */
 };
+
+/* LDPC_F_LAYERED — layered min-sum, fp32, per codeword (conventions of the flooding min-sum: L = -llr, the
+ * magnitude rule, the decision rule):
+ *
+ *   APP_v = L_v + (+0.0f) for every v;  c2v[e] = +0.0f for every edge
+ *   for it in 0 .. iters-1:
+ *     for check c in ascending order:                                        (row-serial)
+ *       for each edge e of c (ascending column):  t_e = APP_v(e) - c2v[e]     (one fp32 subtract)
+ *       min1 <= min2 = the two smallest |t_e|, idx = an edge attaining min1, sgn = xor of the sign bits of t_e
+ *       c2v[e] = (sgn ^ signbit(t_e)) ? -mag : mag,
+ *           mag = min(clamp, max(alpha*m - beta, 0)),  m = (e == idx) ? min2 : min1
+ *       APP_v(e) = t_e + c2v[e]                                               (one fp32 add)
+ *     LDPC_F_EARLY_STOP: after the full sweep, stop the codeword when H * (APP <= 2*ZTHR) = 0
+ *   z_v = 0.5f * APP_v;  bit_v = z_v <= ZTHR;  iters_used = sweeps run
+ *
+ * Every value is one correctly rounded fp32 operation on defined operands (no contraction, no reordered sum),
+ * so the result is defined bit for bit; ties in idx cannot change a value (then min2 == min1).  ZTHR is the
+ * hard-decision threshold of every fp32 decoder here (-1.7881392e-07f).  Implemented for the compiled 802.11n
+ * codes with Z <= 64, LDPC_ALGO_MIN_SUM, fp32, through ldpc_decode_ex / ldpc_decode (host or device
+ * pointers); every other combination (tanh-SP, quantized min-sum, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph
+ * without a compiled QC code, IRA graphs, Z = 81, ldpc_decode_weighted, ldpc_decode_x0,
+ * ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says which.  The flag is additive: ldpc_params and
+ * LDPC_ABI_VERSION are unchanged, and nothing changes while it is clear.  Needs no kernel workspace. */
 
 typedef struct {
     int32_t iters;   /* iterations (maximum when LDPC_F_EARLY_STOP)                         */
@@ -79,7 +103,7 @@ int ldpc_graph_destroy(ldpc_graph* g);
 int ldpc_graph_info(const ldpc_graph* g, int32_t* m, int32_t* n, int32_t* nnz, int32_t* qc_z);
 
 /* The kernel family a decode with these params runs on this graph: "qc-z<Z>" (register-resident
- * quasi-cyclic kernels, 802.11n), "ira-z360" (DVB-S2-structured IRA codes, min-sum, fixed count or early
+ * quasi-cyclic kernels, 802.11n), "qc-z<Z>-layered" (the same codes with LDPC_F_LAYERED), "ira-z360" (DVB-S2-structured IRA codes, min-sum, fixed count or early
  * stop) or
  * "generic-csr" (any H).  Introspection only (benchmarks label their records with it); NULL on bad
  * arguments.  The string is thread-local and valid until the next call on this thread.  No reference

@@ -18,6 +18,7 @@ SRCS = [("abi.hip", "abi.hip.o", []), ("generic.hip", "generic.hip.o", [])] + [
     ("generic_run.hip", f"generic_run_{n}.o", [f"-DRUN_T={t}", f"-DRUN_MS={ms}", f"-DRUN_ES={es}", f"-DRUN_NAME=generic_run_{n}"])
     for (n, t, ms, es) in _RUNS] + [("qc.hip", "qc.hip.o", []), ("qc_sl.hip", "qc_sl.hip.o", []), ("qc_pk.hip", "qc_pk.hip.o", []),
            ("qc_sl_es.hip", "qc_sl_es.hip.o", []), ("qc_es.hip", "qc_es.hip.o", []),
+           ("qc_lay.hip", "qc_lay.hip.o", []),
            ("channel.hip", "channel.hip.o", []), ("ira.hip", "ira.hip.o", [])]
 OUT = os.path.join(HERE, "ldpc_amd", "libldpc_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -33,7 +34,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # otherwise (the loop is latency- and issue-limited at the 128-VGPR / 4-waves budget).
 SCHED = ["-mllvm", "--amdgpu-sched-strategy=iterative-ilp"]
 PER_FILE = {"qc.hip": ["-fno-honor-nans", *SCHED], "qc_sl.hip": ["-fno-honor-nans", *SCHED],
-            "qc_pk.hip": ["-fno-honor-nans"], "qc_sl_es.hip": ["-fno-honor-nans"], "qc_es.hip": ["-fno-honor-nans"]}  # iterative-ilp crashes the register allocator on qc_pk (ROCm 7.2)
+            "qc_pk.hip": ["-fno-honor-nans"], "qc_sl_es.hip": ["-fno-honor-nans"], "qc_es.hip": ["-fno-honor-nans"],
+            "qc_lay.hip": ["-fno-honor-nans"]}  # default scheduler: iterative-ilp timed 1.525 against 1.544 ms on the compressed
+                                                  # layered kernel, runs on different boxes (no difference shown); not timed on the shipped form  # iterative-ilp crashes the register allocator on qc_pk (ROCm 7.2)
 
 
 def _hip_includes(src):

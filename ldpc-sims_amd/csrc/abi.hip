@@ -179,6 +179,23 @@ static bool use_qc(const ldpc_graph* g, const ldpc_params* p) {
     return g->qc && !(p->flags & LDPC_F_FORCE_GENERIC) && qc_supports(g->qc, *p);
 }
 
+// LDPC_F_LAYERED: the layered kernel or nothing (no other path runs that schedule)
+static bool use_lay(const ldpc_graph* g, const ldpc_params* p) {
+    return (p->flags & LDPC_F_LAYERED) && g->qc && !(p->flags & LDPC_F_FORCE_GENERIC) && qc_lay_supports(g->qc, *p);
+}
+// LDPC_OK unless p asks for the layered schedule where it does not exist; the message names what is missing
+static int layered_check(const ldpc_graph* g, const ldpc_params* p) {
+    if (!(p->flags & LDPC_F_LAYERED) || use_lay(g, p)) return LDPC_OK;
+    const char* why = "the code's lifting size: the layered kernel serves Z <= 64";
+    if (p->flags & LDPC_F_FORCE_GENERIC) why = "LDPC_F_FORCE_GENERIC: the generic CSR kernels run the flooding schedule only";
+    else if (!g->qc) why = g->ira ? "an IRA (DVB-S2) graph: layered decoding needs a compiled 802.11n QC code"
+                                  : "a graph without a compiled QC code: layered decoding needs 802.11n (648,1/2) or (1296,2/3)";
+    else if (p->algo == LDPC_ALGO_TANH_SP) why = "tanh sum-product: layered decoding is float min-sum only";
+    else if (p->algo == LDPC_ALGO_QMIN_SUM) why = "quantized min-sum: layered decoding is float min-sum only";
+    else if (p->flags & LDPC_F_F64) why = "LDPC_F_F64: layered decoding is fp32 only";
+    return set_error(LDPC_EUNSUPPORTED, "LDPC_F_LAYERED is not implemented for %s", why);
+}
+
 static bool use_ira(const ldpc_graph* g, const ldpc_params* p) {
     return g->ira && !(p->flags & LDPC_F_FORCE_GENERIC) && ira_supports(g->ira, *p);
 }
@@ -187,6 +204,7 @@ static size_t elem_size(const ldpc_params* p) { return (p->flags & LDPC_F_F64) ?
 
 // Workspace = kernel scratch followed (host-pointer callers only) by staging for llr/bits/soft/used.
 static size_t kernel_ws(const ldpc_graph* g, int64_t B, const ldpc_params* p) {
+    if (use_lay(g, p)) return 0;
     if (use_qc(g, p)) return align256(qc_workspace(g->qc, B, *p));
     if (use_ira(g, p)) return align256(ira_workspace(g->ira, B, *p));
     return align256(generic_workspace(gargs(g), B, *p));
@@ -400,7 +418,9 @@ const char* ldpc_kernel_path(const ldpc_graph* g, const ldpc_params* p) {
         set_error(LDPC_EINVAL, "bad kernel_path query");
         return nullptr;
     }
-    if (use_qc(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc));
+    if (layered_check(g, p) != LDPC_OK) return nullptr;
+    if (use_lay(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc)) + "-layered";
+    else if (use_qc(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc));
     else if (use_ira(g, p)) path = "ira-z360";
     else path = "generic-csr";
     return path.c_str();
@@ -408,6 +428,7 @@ const char* ldpc_kernel_path(const ldpc_graph* g, const ldpc_params* p) {
 
 int ldpc_workspace_size(const ldpc_graph* g, int64_t B, const ldpc_params* p, size_t* bytes) {
     if (!g || !bytes || B < 0 || !params_valid(p)) return set_error(LDPC_EINVAL, "bad workspace query");
+    if (const int rc = layered_check(g, p)) return rc;
     *bytes = kernel_ws(g, B, p) + staging_ws(g, B, p);
     return LDPC_OK;
 }
@@ -419,6 +440,9 @@ static int decode_impl(const ldpc_graph* gc, const void* llr, int64_t B, const l
     if (!g) return set_error(LDPC_EINVAL, "null graph");
     if (!params_valid(p)) return set_error(LDPC_EINVAL, "invalid ldpc_params");
     if (B < 0 || (B > 0 && !llr)) return set_error(LDPC_EINVAL, "llr is null or B < 0");
+    if (w && (p->flags & LDPC_F_LAYERED))
+        return set_error(LDPC_EUNSUPPORTED, "LDPC_F_LAYERED is not implemented for weighted BP / initial messages");
+    if (const int rc = layered_check(g, p)) return rc;
     if (B == 0) return LDPC_OK;
     if (p->algo == LDPC_ALGO_QMIN_SUM && !use_qc(g, p))
         return set_error(LDPC_EUNSUPPORTED, "quantized min-sum needs a QC-specialised graph");
@@ -463,7 +487,9 @@ static int decode_impl(const ldpc_graph* gc, const void* llr, int64_t B, const l
         llr_d = llr_s;
     }
     int rc;
-    if (use_qc(g, p)) {
+    if (use_lay(g, p)) {
+        rc = qc_lay_decode(g->qc, llr_d, B, *p, bits_d, soft_d, used_d, st);
+    } else if (use_qc(g, p)) {
         rc = qc_decode(g->qc, llr_d, B, *p, bits_d, soft_d, used_d, ws, st);
     } else if (use_ira(g, p) && !w) {
         rc = ira_decode(g->ira, (const float*)llr_d, B, *p, bits_d, (float*)soft_d, used_d, ws, st);
@@ -545,6 +571,8 @@ int ldpc_decode_bits_host(const ldpc_graph* gc, const double* llr, int64_t rows,
     if (!params_valid(p)) return set_error(LDPC_EINVAL, "invalid ldpc_params");
     if (p->flags & (LDPC_F_F64 | LDPC_F_DEVICE_PTRS | LDPC_F_SOFT_Z))
         return set_error(LDPC_EINVAL, "decode_bits_host: float32 arithmetic on host buffers, bits only");
+    if (p->flags & LDPC_F_LAYERED)
+        return set_error(LDPC_EUNSUPPORTED, "LDPC_F_LAYERED is not implemented for ldpc_decode_bits_host");
     if (rows == 0) return LDPC_OK;
     const int n = g->n;
     if (chunk <= 0) chunk = std::max<int64_t>(256, ((int64_t)16 << 20) / ((int64_t)n * 4) / 256 * 256);  // ~16 MB of f32

@@ -499,6 +499,12 @@ size_t qc_workspace(const QCSpec* s, int64_t B, const ldpc_params& p);
 int qc_decode(const QCSpec* s, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
               int32_t* iters_used, char* ws, hipStream_t st);
 
+// Layered (row-serial) min-sum for the compiled QC codes with Z <= 64 (qc_lay.hip, LDPC_F_LAYERED): float
+// min-sum only, no workspace, asynchronous on st.
+bool qc_lay_supports(const QCSpec* s, const ldpc_params& p);
+int qc_lay_decode(const QCSpec* s, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
+                  int32_t* iters_used, hipStream_t st);
+
 // tanh-SP register kernels, two passes (qc.hip k_qc_sp_st, qc_sl_sp.h): qc_sp_fork zeroes the list, runs
 // k_sp_zero_scan on st (the waves / units whose LLRs hold an exact zero: [0] = count, [1 .. B] ids, then one flag
 // byte per unit, in the decode's workspace) and forks a second stream from it; the a == 1 rule's pass walks the

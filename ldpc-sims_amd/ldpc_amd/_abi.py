@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(HERE, LIB_NAME)
 
 LDPC_OK, LDPC_EINVAL, LDPC_EHIP, LDPC_ENOMEM, LDPC_EUNSUPPORTED = 0, -1, -2, -3, -4
 ALGO_TANH_SP, ALGO_MIN_SUM, ALGO_QMIN_SUM = 0, 1, 2
-F_EARLY_STOP, F_DEVICE_PTRS, F_F64, F_SOFT_Z, F_FORCE_GENERIC = 1, 2, 4, 8, 16
+F_EARLY_STOP, F_DEVICE_PTRS, F_F64, F_SOFT_Z, F_FORCE_GENERIC, F_LAYERED = 1, 2, 4, 8, 16, 32
 
 # every symbol include/ldpc_abi.h declares (tests/test_abi.py checks the header and the .so agree)
 EXPORTS = (

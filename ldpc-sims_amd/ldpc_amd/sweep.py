@@ -51,7 +51,7 @@ def code_digest(H) -> str:
 
 def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=0.0, snr_db=(0.0,),
         codewords=65536, batch=65536, seed=1, rank=0, world=1, device=0, early_stop=False, qstep=1.0,
-        qmax=15, app_max=127, mod="bpsk", ofdm_size=32, adc_bits=None, clip_ratio=2.0, checkpoint=None):
+        qmax=15, app_max=127, mod="bpsk", ofdm_size=32, adc_bits=None, clip_ratio=2.0, checkpoint=None, schedule="flooding"):
     """Returns dict(snrdb, uncoded_ber, coded_ber, coded_bler, codewords, seconds, resumed_points).
 
     ``mod``: "bpsk" (BPSK/AWGN LLRs), "qpsk-ofdm" (the reference's chain: modulate_bits, transmit_symbols,
@@ -63,6 +63,8 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
     (``gen_qdata``, ``ofdm_functions.py:118-128``; clip = std(rx of the batch) * ``clip_ratio``) and report
     evaluate_quantized.py's ``*_quantized`` metrics and ``wmse_quantized`` (``:122``) next to the
     unquantized ones.
+
+    ``schedule``: "flooding" or "layered" (``Decoder.decode``); recorded in the result's ``config``.
 
     ``checkpoint``: a JSON-lines file of finished points (see the module docstring): points recorded there
     for this exact configuration (every argument that shapes the data or the decode, a digest of H, a
@@ -80,7 +82,7 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
     enc = DeviceEncoder(H, dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     p = dec.params(iters, algo, clamp, alpha, beta, early_stop, "f32", "p1", qmax, app_max, qstep,
-                   device_ptrs=True)
+                   device_ptrs=True, schedule=schedule)
     bmax = min(batch, codewords)
     wsb = dec.workspace_bytes(bmax, p)
     ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
@@ -128,7 +130,7 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
 
     from .dist import allreduce_counts
     config = dict(code=code if isinstance(code, str) else "custom", algo=algo, iters=iters,
-                  clamp=clamp, alpha=alpha, beta=beta, early_stop=early_stop, mod=mod,
+                  clamp=clamp, alpha=alpha, beta=beta, early_stop=early_stop, mod=mod, schedule=schedule,
                   adc_bits=adc_bits, clip_ratio=clip_ratio if adc_bits is not None else None)
     import torch.distributed as dist
     # counters summed over ranks only inside a process group; without one (tests: rank/world given by hand)
@@ -277,6 +279,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--early-stop", action="store_true")
+    ap.add_argument("--schedule", default="flooding", choices=["flooding", "layered"],
+                    help="layered: row-serial min-sum (802.11n codes with Z <= 64, --algo minsum)")
     ap.add_argument("--mod", default="bpsk", choices=["bpsk", "qpsk-ofdm", "16qam-ofdm"])
     ap.add_argument("--adc-bits", type=int, default=None, help="also decode through the AGC-clipped ADC")
     ap.add_argument("--clip-ratio", type=float, default=2.0)
@@ -313,7 +317,8 @@ def main(argv=None):
             dist.init_process_group(backend)
     ckpt = a.checkpoint or (a.out + ".points.jsonl" if a.out else None)
     r = run(a.code, a.algo, a.iters, a.clamp, a.alpha, a.beta, _parse_points(a.snr), a.n, a.batch, a.seed,
-            rank, world, local, a.early_stop, mod=a.mod, adc_bits=a.adc_bits, clip_ratio=a.clip_ratio, checkpoint=ckpt)
+            rank, world, local, a.early_stop, mod=a.mod, adc_bits=a.adc_bits, clip_ratio=a.clip_ratio, checkpoint=ckpt,
+            schedule=a.schedule)
     if rank == 0:
         for i, e in enumerate(r["snrdb"]):
             line = (f"{e:5.2f} dB  uncoded {r['uncoded_ber'][i]:.4e}  coded BER {r['coded_ber'][i]:.4e}  "

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""A/B of the layered against the flooding schedule on bench.py's config [1] workload — (648,1/2) min-sum,
+B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — in one process on one GPU:
+
+  * block error rate of both legs at every Eb/N0 point (ldpc_count_errors), flooding at --flood-iters (50)
+    and layered at --lay-iters (25);
+  * event-timed launches in interleaved pairs (flooding, layered, flooding, ...), each leg cycling over the
+    points as bench.py's timed loop does, under the engine-clock sampler (ldpc_amd/gpuclock.py): per pair the
+    two times and their ratio, so the pair-to-pair spread stands next to the difference it qualifies.
+
+    python scripts/layered_ab.py --out profiles/layered_ab.json [--pairs 12] [--launches 11]
+
+Needs a GPU; writes one JSON record.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ldpc-sims_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--code", default="wifi648_12")
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--ebn0", default="0:0.5:5")
+    ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--clamp", type=float, default=20.0)
+    ap.add_argument("--flood-iters", type=int, default=50)
+    ap.add_argument("--lay-iters", type=int, default=25)
+    ap.add_argument("--pairs", type=int, default=12)
+    ap.add_argument("--launches", type=int, default=11, help="launches per leg of a pair (one cycle over the points)")
+    ap.add_argument("--warmup", type=int, default=22)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "layered_ab.json"))
+    a = ap.parse_args()
+
+    import torch
+    import ldpc_amd
+    from ldpc_amd import _abi
+    from ldpc_amd.gpuclock import ClockSampler
+    from ldpc_amd.synth import DeviceEncoder
+    if not torch.cuda.is_available():
+        raise SystemExit("layered_ab.py measures on a GPU; none is visible")
+    lib = _abi.load()
+    H, _ = ldpc_amd.get_code(a.code)
+    m, n = H.shape
+    k, B = n - m, a.batch
+    dec = ldpc_amd.get_decoder(H, 0)
+    stream = torch.cuda.current_stream()
+    st = stream.cuda_stream
+    lo, step, hi = (float(x) for x in a.ebn0.split(":"))
+    ebn0 = np.round(np.arange(lo, hi + 1e-9, step), 6)
+    info = torch.empty((B, k), dtype=torch.uint8, device="cuda")
+    _abi.check(lib.ldpc_random_bits(info.data_ptr(), B, k, a.seed, 0, st))
+    cw = DeviceEncoder(H, torch.device("cuda", 0)).encode(info)
+    llrs = []
+    for i, e in enumerate(ebn0):  # bench.py's generation: same seeds, same points
+        x = torch.empty((B, n), dtype=torch.float32, device="cuda")
+        sigma = float(np.sqrt(1.0 / (2.0 * (k / n) * 10.0 ** (e / 10.0))))
+        _abi.check(lib.ldpc_awgn_llr(cw.data_ptr(), x.data_ptr(), B, n, sigma, a.seed * 1000 + i, 0, st))
+        llrs.append(x)
+    bits = torch.empty((B, n), dtype=torch.uint8, device="cuda")
+
+    legs = {}
+    for name, iters, sched in (("flooding", a.flood_iters, "flooding"), ("layered", a.lay_iters, "layered")):
+        p = dec.params(iters, "minsum", a.clamp, device_ptrs=True, schedule=sched)
+        wsb = dec.workspace_bytes(B, p)
+        legs[name] = dict(p=p, wsb=wsb, ws=torch.empty((max(wsb, 1),), dtype=torch.uint8, device="cuda"),
+                          iters=iters, kernel_path=dec.kernel_path(p))
+
+    def launch(leg, x):
+        _abi.check(lib.ldpc_decode_ex(dec._h, x.data_ptr(), B, leg["p"], bits.data_ptr(), None, None,
+                                      leg["ws"].data_ptr(), leg["wsb"], st))
+
+    bler = {}
+    for name, leg in legs.items():
+        counts = torch.zeros((len(ebn0), 3), dtype=torch.int64, device="cuda")
+        for i, x in enumerate(llrs):
+            launch(leg, x)
+            _abi.check(lib.ldpc_count_errors(bits.data_ptr(), cw.data_ptr(), B, n, k, counts[i].data_ptr(), st))
+        c = counts.cpu().numpy().astype(np.float64)
+        bler[name] = dict(coded_bler=(c[:, 1] / c[:, 2]).tolist(), coded_ber_info=(c[:, 0] / (c[:, 2] * k)).tolist())
+
+    def timed(leg):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for s in range(a.launches):
+            launch(leg, llrs[s % len(llrs)])
+        e1.record(stream)
+        return e0, e1
+
+    for w in range(a.warmup):
+        launch(legs["flooding" if w % 2 == 0 else "layered"], llrs[w % len(llrs)])
+    sampler = ClockSampler(0)
+    with sampler:
+        events = [(timed(legs["flooding"]), timed(legs["layered"])) for _ in range(a.pairs)]  # no gap between legs
+        torch.cuda.synchronize()
+    pairs = []
+    for (f0, f1), (l0, l1) in events:
+        f, l = f0.elapsed_time(f1) / a.launches, l0.elapsed_time(l1) / a.launches
+        pairs.append(dict(flooding_ms=f, layered_ms=l, layered_over_flooding_cw_per_s=f / l))
+    ratios = [q["layered_over_flooding_cw_per_s"] for q in pairs]
+    out = dict(code=a.code, batch=B, ebn0_db=ebn0.tolist(), seed=a.seed, clamp=a.clamp, launches_per_leg=a.launches,
+               library=_abi.library_digest(), device=torch.cuda.get_device_name(0),
+               legs={nm: dict(iters=lg["iters"], kernel_path=lg["kernel_path"], **bler[nm]) for nm, lg in legs.items()},
+               pairs=pairs, clock=sampler.summary())
+    for nm, key in (("flooding", "flooding_ms"), ("layered", "layered_ms")):
+        ms = [q[key] for q in pairs]
+        out["legs"][nm].update(launch_ms_median=statistics.median(ms), launch_ms_min=min(ms), launch_ms_max=max(ms),
+                               ms_per_sweep=statistics.median(ms) / legs[nm]["iters"],
+                               cw_per_s=B / (statistics.median(ms) * 1e-3))
+    out["ratio_median"] = statistics.median(ratios)
+    out["ratio_min"], out["ratio_max"] = min(ratios), max(ratios)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps({kk: out[kk] for kk in ("ratio_median", "ratio_min", "ratio_max")}))
+    for nm in legs:
+        lg = out["legs"][nm]
+        print(nm, lg["kernel_path"], f"{lg['iters']} it  {lg['launch_ms_median']:.4f} ms/launch  {lg['ms_per_sweep'] * 1e3:.2f} us/sweep  "
+              f"{lg['cw_per_s'] / 1e6:.2f} M cw/s")
+    print("Eb/N0  BLER flooding  BLER layered")
+    for i, e in enumerate(ebn0):
+        print(f"{e:5.2f}  {out['legs']['flooding']['coded_bler'][i]:.5f}       {out['legs']['layered']['coded_bler'][i]:.5f}")
+
+
+if __name__ == "__main__":
+    main()
