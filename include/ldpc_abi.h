@@ -199,6 +199,18 @@ int ldpc_awgn_llr(const uint8_t* codeword, float* llr, int64_t B, int32_t n, flo
  * so the bits of global codeword b0+b do not depend on how a sweep is sharded.  out: device uint8 [B][k]. */
 int ldpc_random_bits(uint8_t* out, int64_t B, int32_t k, uint64_t seed, int64_t b0, void* stream);
 
+/* Systematic encoding on device: codeword[b] = [info[b] ; parity], H * codeword = 0.
+ *   info      device uint8 [B][k], k = n - m; only bit 0 of each byte is used
+ *   codeword  device uint8 [B][n], values 0/1; must not overlap info
+ * Asynchronous on stream, graph-capturable, needs no workspace.  Implemented for graphs carrying a compiled
+ * 802.11n QC code (Z = 27, 54, 81) and for IRA (staircase) graphs; any other graph: LDPC_EUNSUPPORTED.  The
+ * parity part of H is invertible for these codes, so the parity bits are unique: the result is defined bit for
+ * bit.  Additive: LDPC_ABI_VERSION is unchanged. */
+int ldpc_encode(const ldpc_graph* g, const uint8_t* info, int64_t B, uint8_t* codeword, void* stream);
+
+/* "qc-z<Z>-dualdiag", "ira-staircase", or "none" (thread-local string, as ldpc_kernel_path). */
+const char* ldpc_encoder_path(const ldpc_graph* g);
+
 /* OFDM transmitter, the reference's modulate_bits + transmit_symbols (ofdm/ofdm_functions.py:17-35):
  * bits[nsym * bits_per_symbol] (uint8, device) -> symbols (QPSK bits_per_symbol = 2, the reference's
  * mapping; 16-QAM = 4, Gray per dimension, new) -> blocks of ofdm_size -> unitary IDFT -> + complex AWGN

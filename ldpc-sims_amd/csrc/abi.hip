@@ -634,6 +634,35 @@ int ldpc_count_errors(const uint8_t* bits, const uint8_t* ref, int64_t B, int32_
     return LDPC_OK;
 }
 
+const char* ldpc_encoder_path(const ldpc_graph* g) {
+    static thread_local std::string path;
+    if (!g) {
+        set_error(LDPC_EINVAL, "null graph");
+        return nullptr;
+    }
+    if (qc_encode_supports(g->qc)) path = "qc-z" + std::to_string(qc_z(g->qc)) + "-dualdiag";
+    else if (g->ira) path = "ira-staircase";
+    else path = "none";
+    return path.c_str();
+}
+
+int ldpc_encode(const ldpc_graph* g, const uint8_t* info, int64_t B, uint8_t* codeword, void* stream) {
+    if (!g) return set_error(LDPC_EINVAL, "null graph");
+    if (B < 0 || (B > 0 && (!info || !codeword))) return set_error(LDPC_EINVAL, "info or codeword is null, or B < 0");
+    const bool qc = qc_encode_supports(g->qc);
+    if (!qc && !g->ira)
+        return set_error(LDPC_EUNSUPPORTED, "ldpc_encode is implemented for the compiled 802.11n QC codes and for IRA "
+                                            "(staircase) graphs; this graph is neither");
+    if (B == 0) return LDPC_OK;
+    const int k = g->n - g->m;
+    if (info < codeword + (size_t)B * g->n && codeword < info + (size_t)B * k)
+        return set_error(LDPC_EINVAL, "codeword overlaps info");
+    DeviceGuard dg(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (qc) return qc_encode(g->qc, info, B, codeword, st);
+    return ira_encode(g->d_row_ptr, g->d_col_idx, g->m, g->n, info, B, codeword, st);
+}
+
 int ldpc_awgn_llr(const uint8_t* codeword, float* llr, int64_t B, int32_t n, float sigma, uint64_t seed, int64_t b0,
                   void* stream) {
     if (!llr || B < 0 || n <= 0 || !(sigma > 0.0f) || b0 < 0) return set_error(LDPC_EINVAL, "bad awgn arguments");

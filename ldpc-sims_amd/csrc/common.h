@@ -505,6 +505,14 @@ bool qc_lay_supports(const QCSpec* s, const ldpc_params& p);
 int qc_lay_decode(const QCSpec* s, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
                   int32_t* iters_used, hipStream_t st);
 
+// Systematic encoders (encode.hip, ldpc_encode): the compiled 802.11n codes from their dual-diagonal parity
+// part, IRA graphs from the CSR's staircase.  info [B][k] -> cw [B][n], device pointers, asynchronous on st,
+// no workspace.
+bool qc_encode_supports(const QCSpec* s);
+int qc_encode(const QCSpec* s, const uint8_t* info, int64_t B, uint8_t* cw, hipStream_t st);
+int ira_encode(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, const uint8_t* info, int64_t B,
+               uint8_t* cw, hipStream_t st);
+
 // tanh-SP register kernels, two passes (qc.hip k_qc_sp_st, qc_sl_sp.h): qc_sp_fork zeroes the list, runs
 // k_sp_zero_scan on st (the waves / units whose LLRs hold an exact zero: [0] = count, [1 .. B] ids, then one flag
 // byte per unit, in the decode's workspace) and forks a second stream from it; the a == 1 rule's pass walks the

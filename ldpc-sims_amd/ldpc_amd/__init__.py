@@ -3,12 +3,12 @@
 Drop-in for the decode path of realjwin/ldpc-sims (pytorch/bp + ofdm_functions.decode_bits).
 """
 from . import _abi, codes
-from .api import Decoder, decode, decode_bits, decoder, get_decoder
+from .api import Decoder, decode, decode_bits, decoder, encode, get_decoder
 from .codes import Encoder, Graph, QCCode, get_code, peg_64_32, qc_expand, wifi_code
 
 _abi.load()  # fail loudly at import if the HIP library is missing: there is no CPU fallback
 
-__all__ = ["Decoder", "decode", "decode_bits", "decoder", "get_decoder", "BeliefPropagation", "codes",
+__all__ = ["Decoder", "decode", "decode_bits", "decoder", "encode", "get_decoder", "BeliefPropagation", "codes",
            "Encoder", "Graph", "QCCode", "get_code", "peg_64_32", "qc_expand", "wifi_code"]
 
 

@@ -22,7 +22,7 @@ EXPORTS = (
     "ldpc_workspace_size", "ldpc_decode_ex", "ldpc_decode", "ldpc_count_errors", "ldpc_awgn_llr",
     "ldpc_random_bits", "ldpc_ofdm_tx", "ldpc_ofdm_demod", "ldpc_adc_quantize", "ldpc_weights_layout",
     "ldpc_decode_weighted", "ldpc_decode_x0", "ldpc_decode_bits_host", "ldpc_last_error", "ldpc_device_count",
-    "ldpc_version", "ldpc_kernel_path", "ldpc_abi_version",
+    "ldpc_version", "ldpc_kernel_path", "ldpc_abi_version", "ldpc_encode", "ldpc_encoder_path",
 )
 ABI_VERSION = 2  # LDPC_ABI_VERSION of include/ldpc_abi.h this binding is written for
 
@@ -98,12 +98,15 @@ def load(path: str | None = None):
     for f in ("ldpc_graph_create", "ldpc_graph_create_qc", "ldpc_graph_destroy", "ldpc_graph_info",
               "ldpc_workspace_size", "ldpc_decode_ex", "ldpc_decode", "ldpc_count_errors", "ldpc_awgn_llr",
               "ldpc_random_bits", "ldpc_ofdm_tx", "ldpc_ofdm_demod", "ldpc_adc_quantize", "ldpc_weights_layout", "ldpc_decode_weighted",
-              "ldpc_decode_x0", "ldpc_decode_bits_host", "ldpc_device_count", "ldpc_abi_version"):
+              "ldpc_decode_x0", "ldpc_decode_bits_host", "ldpc_device_count", "ldpc_abi_version", "ldpc_encode"):
         getattr(L, f).restype = ctypes.c_int
     L.ldpc_last_error.restype = ctypes.c_char_p
     L.ldpc_version.restype = ctypes.c_char_p
     L.ldpc_kernel_path.argtypes = [vp, ctypes.POINTER(Params)]
     L.ldpc_kernel_path.restype = ctypes.c_char_p
+    L.ldpc_encode.argtypes = [vp, vp, i64, vp, vp]
+    L.ldpc_encoder_path.argtypes = [vp]
+    L.ldpc_encoder_path.restype = ctypes.c_char_p
     L._ldpc_path = p
     if path is None:
         _lib = L

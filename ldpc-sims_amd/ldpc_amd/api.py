@@ -93,6 +93,39 @@ class Decoder:
             raise _abi.LdpcError(_abi.LDPC_EINVAL, self.lib.ldpc_last_error().decode(errors="replace"))
         return s.decode()
 
+    @property
+    def encoder_path(self) -> str:
+        """The kernel ``encode`` runs on this graph: "qc-z<Z>-dualdiag", "ira-staircase" or "none"."""
+        return self.lib.ldpc_encoder_path(self._h).decode()
+
+    def encode(self, info, out=None, stream=None):
+        """Systematic encoding of a (B, k) batch of information bits (uint8, bit 0 of each byte) into (B, n)
+        codewords [info ; parity] with H * codeword = 0 (``ldpc_encode``) — the bits ``codes.Encoder`` /
+        ``codes.IRAEncoder`` give.  A torch GPU tensor on this decoder's device -> a torch GPU tensor (``out``
+        when given: uint8, (B, n), contiguous), on ``stream`` (a ``torch.cuda.Stream``; default: the current
+        stream) without synchronising; ordering a side stream against the producers of ``info`` and the users of
+        the result is the caller's.  A numpy array is copied in and the result copied out.  Graphs without an
+        encoder raise ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
+        torch = _torch()
+        k = self.n - self.m
+        on_gpu = type(info).__module__.startswith("torch") and info.is_cuda
+        dev = torch.device("cuda", self.device)
+        if on_gpu and info.device != dev:
+            raise ValueError(f"info is on {info.device}, this decoder's graph is on {dev}")
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(st):  # copies, the output and the kernel all live on st
+            x = info if on_gpu else torch.from_numpy(np.array(info, dtype=np.uint8, order="C")).to(dev)
+            if x.dtype != torch.uint8 or x.dim() != 2 or x.shape[1] != k:
+                raise RuntimeError(f"info must be uint8 (B, {k}), got {x.dtype} {tuple(x.shape)}")
+            x = x.contiguous()
+            B = x.shape[0]
+            cw = torch.empty((B, self.n), dtype=torch.uint8, device=dev) if out is None else out
+            if (cw.dtype != torch.uint8 or tuple(cw.shape) != (B, self.n) or cw.device != dev
+                    or not cw.is_contiguous()):
+                raise RuntimeError(f"out must be a contiguous uint8 ({B}, {self.n}) tensor on {dev}")
+            check(self.lib.ldpc_encode(self._h, x.data_ptr(), B, cw.data_ptr(), ctypes.c_void_p(st.cuda_stream)))
+            return cw if on_gpu else cw.cpu().numpy()
+
     def workspace_bytes(self, B: int, p: Params) -> int:
         out = ctypes.c_size_t()
         check(self.lib.ldpc_workspace_size(self._h, int(B), ctypes.byref(p), ctypes.byref(out)))
@@ -261,6 +294,15 @@ def decode(H, llr, max_iters: int, *, algo="tanh", clamp=10.0, alpha=1.0, beta=0
     if out == "bits":
         return r["bits"]
     return r
+
+
+def encode(H, info, *, device=None):
+    """``encode(H, info)`` -> codewords (uint8, (B, n)) of the (B, k) information bits on the GPU
+    (``Decoder.encode``): torch GPU tensor in -> torch GPU tensor out, numpy in -> numpy out."""
+    on_gpu = type(info).__module__.startswith("torch") and info.is_cuda
+    if device is None:
+        device = info.device.index if on_gpu else 0
+    return get_decoder(H, device or 0).encode(info)
 
 
 class _OutputPool:

@@ -51,7 +51,8 @@ def code_digest(H) -> str:
 
 def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=0.0, snr_db=(0.0,),
         codewords=65536, batch=65536, seed=1, rank=0, world=1, device=0, early_stop=False, qstep=1.0,
-        qmax=15, app_max=127, mod="bpsk", ofdm_size=32, adc_bits=None, clip_ratio=2.0, checkpoint=None, schedule="flooding"):
+        qmax=15, app_max=127, mod="bpsk", ofdm_size=32, adc_bits=None, clip_ratio=2.0, checkpoint=None, schedule="flooding",
+        encoder="auto"):
     """Returns dict(snrdb, uncoded_ber, coded_ber, coded_bler, codewords, seconds, resumed_points).
 
     ``mod``: "bpsk" (BPSK/AWGN LLRs), "qpsk-ofdm" (the reference's chain: modulate_bits, transmit_symbols,
@@ -66,6 +67,11 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
 
     ``schedule``: "flooding" or "layered" (``Decoder.decode``); recorded in the result's ``config``.
 
+    ``encoder``: "auto" (default) encodes with the library's HIP encoder (``Decoder.encode``) where the graph
+    has one (``Decoder.encoder_path``) and with ``synth.DeviceEncoder`` (torch arithmetic) otherwise; "torch"
+    always uses ``DeviceEncoder``.  The codewords are the same bits either way, so the argument is not part of
+    ``config``, the checkpoint key or the result.
+
     ``checkpoint``: a JSON-lines file of finished points (see the module docstring): points recorded there
     for this exact configuration (every argument that shapes the data or the decode, a digest of H, a
     digest of the decoder library, the point's index and value, the world size) are taken from it instead
@@ -79,7 +85,10 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
     dec = get_decoder(H, device)
     lib = _abi.load()
     dev = torch.device("cuda", device)
-    enc = DeviceEncoder(H, dev)
+    if encoder not in ("auto", "torch"):
+        raise ValueError("encoder must be 'auto' or 'torch'")
+    hip_enc = encoder == "auto" and dec.encoder_path != "none"
+    enc = None if hip_enc else DeviceEncoder(H, dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     p = dec.params(iters, algo, clamp, alpha, beta, early_stop, "f32", "p1", qmax, app_max, qstep,
                    device_ptrs=True, schedule=schedule)
@@ -89,6 +98,7 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
     info = torch.empty((bmax, k), dtype=torch.uint8, device=dev)
     llr = torch.empty((bmax, n), dtype=torch.float32, device=dev)
     bits = torch.empty((bmax, n), dtype=torch.uint8, device=dev)
+    cwbuf = torch.empty((bmax, n), dtype=torch.uint8, device=dev) if hip_enc else None
     unc = torch.zeros((len(snr_db),), dtype=torch.int64, device=dev)
     if adc_bits is not None and mod == "bpsk":
         raise ValueError("adc_bits needs an OFDM modulation (the ADC sees the time-domain samples)")
@@ -101,7 +111,7 @@ def run(code="wifi648_12", algo="minsum", iters=50, clamp=20.0, alpha=1.0, beta=
         for s in range(lo, hi, bmax):
             B = min(bmax, hi - s)
             _abi.check(lib.ldpc_random_bits(info.data_ptr(), B, k, seed * 7919 + i, s, st))
-            cw = enc.encode(info[:B])
+            cw = dec.encode(info[:B], out=cwbuf[:B]) if hip_enc else enc.encode(info[:B])
             if mod == "bpsk":
                 _abi.check(lib.ldpc_awgn_llr(cw.data_ptr(), llr.data_ptr(), B, n, sigma, seed * 104729 + i, s, st))
             else:
@@ -281,6 +291,8 @@ def main(argv=None):
     ap.add_argument("--early-stop", action="store_true")
     ap.add_argument("--schedule", default="flooding", choices=["flooding", "layered"],
                     help="layered: row-serial min-sum (802.11n codes with Z <= 64, --algo minsum)")
+    ap.add_argument("--encoder", default="auto", choices=["auto", "torch"],
+                    help="auto: the library's HIP encoder where the code has one; torch: synth.DeviceEncoder")
     ap.add_argument("--mod", default="bpsk", choices=["bpsk", "qpsk-ofdm", "16qam-ofdm"])
     ap.add_argument("--adc-bits", type=int, default=None, help="also decode through the AGC-clipped ADC")
     ap.add_argument("--clip-ratio", type=float, default=2.0)
@@ -318,7 +330,7 @@ def main(argv=None):
     ckpt = a.checkpoint or (a.out + ".points.jsonl" if a.out else None)
     r = run(a.code, a.algo, a.iters, a.clamp, a.alpha, a.beta, _parse_points(a.snr), a.n, a.batch, a.seed,
             rank, world, local, a.early_stop, mod=a.mod, adc_bits=a.adc_bits, clip_ratio=a.clip_ratio, checkpoint=ckpt,
-            schedule=a.schedule)
+            schedule=a.schedule, encoder=a.encoder)
     if rank == 0:
         for i, e in enumerate(r["snrdb"]):
             line = (f"{e:5.2f} dB  uncoded {r['uncoded_ber'][i]:.4e}  coded BER {r['coded_ber'][i]:.4e}  "
