@@ -147,15 +147,8 @@ __device__ __forceinline__ float sp_vn_arg(float L, float sum2) { return __built
 #ifndef DS_CR
 #define DS_CR 0
 #endif
-// DS_DIAG_NOTRANS (DIAGNOSTIC BUILDS ONLY, wrong results): the three transcendentals (v_exp_f32 here, v_rcp_f32 and
-// v_log_f32 in ds_out) replaced by one fma each, to price what their issue cost and latency take from a kernel
-#ifndef DS_DIAG_NOTRANS
-#define DS_DIAG_NOTRANS 0
-#endif
 __device__ __forceinline__ float vn_signed_a(float x2) {
-#if DS_DIAG_NOTRANS
-    return __builtin_copysignf(__builtin_fmaf(-fabsf(x2), 0x1p-6f, 1.0f), x2);
-#elif DS_CR & 1
+#if DS_CR & 1
     return __builtin_copysignf((float)exp2(-(double)fabsf(x2)), x2);
 #else
     return __builtin_copysignf(__builtin_amdgcn_exp2f(-fabsf(x2)), x2);
@@ -165,16 +158,9 @@ __device__ __forceinline__ float vn_signed_a(float x2) {
 // SP_TIE(operands): the serial-chain tie of the tanh-SP kernels, an empty asm that redefines the chain's
 // values (so the next edge's chain depends on this edge's output).  Its cost: the hazard recognizer takes an
 // asm-defined VGPR for a possible transcendental result, so a VALU reading it right after gets an s_nop
-// (~100 of the (648,1/2) loop's 231).  SP_TIE_SCHED (a scheduling barrier instead, no operands) spills
-// 46 VGPRs there and 287 in the sliced kernel: not used.
-#ifndef SP_TIE_SCHED
-#define SP_TIE_SCHED 0
-#endif
-#if SP_TIE_SCHED
-#define SP_TIE(...) __builtin_amdgcn_sched_barrier(0)
-#else
+// (~100 of the (648,1/2) loop's 231).  A scheduling barrier instead (no operands) spills 46 VGPRs there and 287
+// in the sliced kernel.
 #define SP_TIE(...) asm volatile("" : __VA_ARGS__)
-#endif
 
 // VC exclusive sums of one column of compile-time degree d in O(d) — 3d - 6 adds instead of the ~d^2 / 2 of
 // re-summing the others per edge; the oracle's stable form (sp_f32_one) sums in the same order:
@@ -218,39 +204,27 @@ __device__ __forceinline__ DSet ds_push(DSet x, float a) {  // a = |signed a| of
 // log2(S/D) of a set clamped to [0, cmax2] (S >= D; a rounding below 1 gives 0; D == 0: +inf -> cmax2), with
 // the given sign bit (bit 31 of sgn)
 __device__ __forceinline__ float ds_out(float D, float S, uint32_t sgn, float cmax2) {
-#if DS_DIAG_NOTRANS
-    const float r = __builtin_fmaf(S, 0.5f, D);
-#elif DS_CR & 2
+#if DS_CR & 2
     const float r = (float)((double)S / (double)D);  // S, D exact in fp64: one rounding = the oracle's S / D
 #else
     const float r = S * __builtin_amdgcn_rcpf(D);
 #endif
-#if DS_DIAG_NOTRANS
-    const float y = __builtin_amdgcn_fmed3f(__builtin_fmaf(r, 0.25f, -1.0f), 0.0f, cmax2);
-#elif DS_CR & 4
+#if DS_CR & 4
     const float y = __builtin_amdgcn_fmed3f((float)log2((double)r), 0.0f, cmax2);
 #else
     const float y = __builtin_amdgcn_fmed3f(__builtin_amdgcn_logf(r), 0.0f, cmax2);
 #endif
     return u2f(f2u(y) | (sgn & 0x80000000u));
 }
-// the output of an edge from its prefix set p and suffix set q (the join, then ds_out).  DS_JOIN_FMA: each of
+// the output of an edge from its prefix set p and suffix set q (the join, then ds_out): each of
 // D and S is one product and one fma (D = fma(p.D, q.S, p.S * q.D), S = fma(p.D, q.D, p.S * q.S)), 4 VALU per
 // join instead of 6 (two products and an add each); both round at most twice, as before.  A symmetric suffix
 // (q.D == q.S: it holds an edge with a = 1, s = +-0) still gives D == S exactly — both are fma(p.D, x, p.S * x)
 // — so such an edge zeroes the others' outputs as the reference's p = 0; a symmetric prefix gives D, S within
 // an ulp (an output <= 2^-23 in log2 units instead of 0).  The oracle (ldpc_oracle.c cn_stable_f32) joins the same way.
-#ifndef DS_JOIN_FMA
-#define DS_JOIN_FMA 1
-#endif
 __device__ __forceinline__ float ds_join_out(DSet p, DSet q, uint32_t sgn, float cmax2) {
-#if DS_JOIN_FMA
     const float D = __builtin_fmaf(p.D, q.S, p.S * q.D);
     const float S = __builtin_fmaf(p.D, q.D, p.S * q.S);
-#else
-    const float D = p.D * q.S + p.S * q.D;  // -ffp-contract=off: two products and one add each
-    const float S = p.S * q.S + p.D * q.D;
-#endif
     return ds_out(D, S, sgn, cmax2);
 }
 
@@ -265,9 +239,6 @@ __device__ __forceinline__ float ds_join_out(DSet p, DSet q, uint32_t sgn, float
 #ifndef DS_BLOCK
 #define DS_BLOCK 7  // (1944,5/6) d = 20: 3 blocks, 128 VGPRs spill-free at 4 waves/SIMD (10: 3 VGPRs spilled)
 #endif
-#ifndef DS_TSHARE
-#define DS_TSHARE 1
-#endif
 // LAG = 1 (with SERIAL = 1): the running prefix after edge t is tied to edge t - 1's output instead of edge t's,
 // so edge t's output (rcp, log) overlaps edge t + 1's join — two edges in flight, same operations.
 template <int t, int LAG, int d>
@@ -277,7 +248,7 @@ __device__ __forceinline__ void ds_tie(DSet& pre, float (&g)[d]) {
 }
 // Edges with a == 1 (s = +-0: the reference's tanh(0) = 0 makes p exactly 0 for every OTHER edge of the check,
 // bp_cv.py:38-50): an edge whose exclusive set holds one outputs exactly +-0 (oracle cn_stable_f32).  The (D, S)
-// sets give that by themselves except through a join with such a PREFIX (an ulp apart, DS_JOIN_FMA) and S/D
+// sets give that by themselves except through a join with such a PREFIX (an ulp apart, ds_join_out) and S/D
 // rounded through v_rcp_f32, and several such edges per check (erasures, quantized LLRs) add up to a flipped
 // hard decision (tests/golden/bp_zeros.npz).  cn_ds_row<..., FIX = true> marks the row's a == 1 edges in the low
 // bits of the row's sign word (whose bit 31 alone the outputs read, so no register is added) and resets each
@@ -288,9 +259,6 @@ __device__ __forceinline__ void ds_tie(DSet& pre, float (&g)[d]) {
 // cancellation, or |s| so small that exp rounds to 1) leaves its partners within 2^-23 (log2 units) of 0.  The
 // register kernels run the FIX loop for a wave / unit with such a codeword (fixm masks the lanes of its other
 // codeword), the plain loop otherwise; the generic kernels read a flag per codeword (k_load_llr).
-#ifndef QC_SP_FIXZ
-#define QC_SP_FIXZ 1  // register kernels: the FIX loop for waves / units with an exact-zero LLR (0: never)
-#endif
 template <int d>
 __device__ __forceinline__ uint32_t ds_ones(const float (&g)[d]) {
     uint32_t ones = 0;
@@ -333,45 +301,32 @@ __device__ __forceinline__ void cn_ds_row(float (&g)[d], float cmax2, uint32_t f
         // the compiler CSEs the passes and keeps every suffix set live, which is what blocking avoids.)
         constexpr int BS = BLOCK < d ? BLOCK : d, NBK = (d + BS - 1) / BS;
         DSet pre = {0.0f, 1.0f};
-        // DS_TSHARE: one pass from the row's end yields every block's T (the sets at the block boundaries,
+        // one pass from the row's end yields every block's T (the sets at the block boundaries,
         // the same pushes in the same order), instead of a fresh pass per block
-        [[maybe_unused]] float TD[NBK], TS[NBK];
-        if constexpr (DS_TSHARE) {
-            float a = fabsf(g[d - 1]);
-            asm volatile("" : "+v"(a));
-            DSet T = {a, 1.0f};
-            if constexpr ((d - 1) % BS == 0) {  // a block ends at hi = d - 1: its T is the last edge alone
-                TD[(d - 1) / BS - 1] = T.D;
-                TS[(d - 1) / BS - 1] = T.S;
-            }
-            static_for<0, d - 1 - BS>([&](auto uu) __attribute__((always_inline)) {
-                constexpr int t = d - 2 - decltype(uu)::value;  // d-2 down to BS
-                float b = fabsf(g[t]);
-                asm volatile("" : "+v"(b));
-                T = ds_push(T, b);
-                if constexpr (t % BS == 0) {  // t = hi of block t / BS - 1
-                    TD[t / BS - 1] = T.D;
-                    TS[t / BS - 1] = T.S;
-                }
-            });
+        float TD[NBK], TS[NBK];
+        float a = fabsf(g[d - 1]);
+        asm volatile("" : "+v"(a));
+        DSet T = {a, 1.0f};
+        if constexpr ((d - 1) % BS == 0) {  // a block ends at hi = d - 1: its T is the last edge alone
+            TD[(d - 1) / BS - 1] = T.D;
+            TS[(d - 1) / BS - 1] = T.S;
         }
+        static_for<0, d - 1 - BS>([&](auto uu) __attribute__((always_inline)) {
+            constexpr int t = d - 2 - decltype(uu)::value;  // d-2 down to BS
+            float b = fabsf(g[t]);
+            asm volatile("" : "+v"(b));
+            T = ds_push(T, b);
+            if constexpr (t % BS == 0) {  // t = hi of block t / BS - 1
+                TD[t / BS - 1] = T.D;
+                TS[t / BS - 1] = T.S;
+            }
+        });
         static_for<0, NBK>([&](auto kk) __attribute__((always_inline)) {
             constexpr int lo = decltype(kk)::value * BS, hi = (lo + BS < d) ? lo + BS : d;
             float sD[BS + 1], sS[BS + 1];  // sD[t - lo]: set of edges t..d-1, lo < t <= hi
-            if constexpr (hi < d && DS_TSHARE) {
+            if constexpr (hi < d) {
                 sD[hi - lo] = TD[decltype(kk)::value];
                 sS[hi - lo] = TS[decltype(kk)::value];
-            } else if constexpr (hi < d) {
-                float a = fabsf(g[d - 1]);
-                asm volatile("" : "+v"(a));
-                DSet T = {a, 1.0f};
-                static_for<0, d - 1 - hi>([&](auto uu) __attribute__((always_inline)) {
-                    float b = fabsf(g[d - 2 - decltype(uu)::value]);
-                    asm volatile("" : "+v"(b));
-                    T = ds_push(T, b);
-                });
-                sD[hi - lo] = T.D;
-                sS[hi - lo] = T.S;
             }
             static_for<0, hi - lo - 1>([&](auto uu) __attribute__((always_inline)) {
                 constexpr int t = hi - 1 - decltype(uu)::value;  // hi-1 down to lo+1
@@ -525,7 +480,7 @@ __host__ __device__ inline uint8_t* qc_sp_zflag(uint32_t* zlist, int64_t B) {
 int qc_sp_fork(const float* llr, int64_t B, int n, int cpu, hipStream_t st, hipStream_t* s2);
 int qc_sp_join(hipStream_t st);
 // up to 3 extra streams per (host thread, device, caller stream), forked from / joined back into the caller's stream
-// by events (graph-capturable); one fork / join pair at a time per caller stream and thread (qc.hip)
+// by events (graph-capturable); one fork / join pair at a time per caller stream and thread (aux_streams.hip)
 int aux_fork(hipStream_t st, hipStream_t* s2, int n = 1);
 int aux_join(hipStream_t st, int n = 1);
 constexpr unsigned kSpPass2Blocks = 1280;  // second-pass grid cap: 5 units per CU

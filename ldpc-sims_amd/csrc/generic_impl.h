@@ -72,25 +72,11 @@ __device__ __forceinline__ bool tile_slot(int nodes, int tpl2, int64_t B, int& n
     return node < nodes && cw < B;
 }
 
-// Message streams are read once and written once per iteration: GEN_NT_LOAD / GEN_NT_STORE build
-// variants with non-temporal ("nt") cache policy on them (A/B, scripts/mkvariant.sh).
-#ifndef GEN_NT_LOAD
-#define GEN_NT_LOAD 0
-#endif
-// GEN_SKIP_DUP: the min-sum kernels load only the d < MAXD edges a node has (d is wave-uniform: a scalar
-// branch per slot) instead of re-loading the last edge into the unused slots (cache hits, but TA / L2 requests:
-// DVB-S2's variables have degree 8, 3 or 2 under MAXD = 8)
 #ifndef GEN_VW_CAP
 #define GEN_VW_CAP 16  // A/B knob: at most this many codewords per thread in the streaming kernels' wide tiles
 #endif
 #ifndef GEN_TPL2_MAX
 #define GEN_TPL2_MAX 8  // A/B knob: at most 2^GEN_TPL2_MAX threads per node (the rest of the 256 take other nodes)
-#endif
-#ifndef GEN_SKIP_DUP
-#define GEN_SKIP_DUP 0
-#endif
-#ifndef GEN_NT_STORE
-#define GEN_NT_STORE 0
 #endif
 
 template <typename T, int V>
@@ -102,11 +88,11 @@ __device__ __forceinline__ Vec<T, V> vload(const T* p) {
     Vec<T, V> r;
     if constexpr (V * sizeof(T) == 16) {
         using U = __attribute__((ext_vector_type(4))) float;
-        const U u = GEN_NT_LOAD ? __builtin_nontemporal_load(reinterpret_cast<const U*>(p)) : *reinterpret_cast<const U*>(p);
+        const U u = *reinterpret_cast<const U*>(p);
         __builtin_memcpy(r.x, &u, 16);
     } else if constexpr (V * sizeof(T) == 8) {
         using U = __attribute__((ext_vector_type(2))) float;
-        const U u = GEN_NT_LOAD ? __builtin_nontemporal_load(reinterpret_cast<const U*>(p)) : *reinterpret_cast<const U*>(p);
+        const U u = *reinterpret_cast<const U*>(p);
         __builtin_memcpy(r.x, &u, 8);
     } else {
 #pragma unroll
@@ -120,14 +106,12 @@ __device__ __forceinline__ void vstore(T* p, const Vec<T, V>& r) {
         using U = __attribute__((ext_vector_type(4))) float;
         U u;
         __builtin_memcpy(&u, r.x, 16);
-        if constexpr (GEN_NT_STORE) __builtin_nontemporal_store(u, reinterpret_cast<U*>(p));
-        else *reinterpret_cast<U*>(p) = u;
+        *reinterpret_cast<U*>(p) = u;
     } else if constexpr (V * sizeof(T) == 8) {
         using U = __attribute__((ext_vector_type(2))) float;
         U u;
         __builtin_memcpy(&u, r.x, 8);
-        if constexpr (GEN_NT_STORE) __builtin_nontemporal_store(u, reinterpret_cast<U*>(p));
-        else *reinterpret_cast<U*>(p) = u;
+        *reinterpret_cast<U*>(p) = u;
     } else {
 #pragma unroll
         for (int i = 0; i < V; ++i) p[i] = r.x[i];
@@ -481,7 +465,6 @@ __global__ __launch_bounds__(256) void k_vn_ms(const int32_t* __restrict__ var_p
 #pragma unroll
     for (int k = 0; k < MAXD; ++k) {
         off[k] = (int64_t)var_edges[a + (k < d ? k : d - 1)] * ldb + cw;
-        if (GEN_SKIP_DUP && k >= d) continue;  // d is wave-uniform: a scalar branch, the loop stays unrolled
         if (first) {
 #pragma unroll
             for (int i = 0; i < V; ++i) x[k].x[i] = 0.0f;
@@ -524,7 +507,6 @@ __global__ __launch_bounds__(256) void k_cn_ms(const int32_t* __restrict__ row_p
     Vec<float, V> t[MAXD];
 #pragma unroll
     for (int k = 0; k < MAXD; ++k) {
-        if (GEN_SKIP_DUP && k >= d) continue;  // d is wave-uniform: a scalar branch, the loop stays unrolled
         t[k] = vload<float, V>(v2c + (int64_t)(a + (k < d ? k : d - 1)) * ldb + cw);
     }
 #pragma unroll

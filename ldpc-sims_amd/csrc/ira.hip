@@ -25,7 +25,7 @@
 // + states read and written (24M) in the CN = 16n + 36M = 2.1 MB for DVB-S2 1/2, against 3.89 MB for the
 // two-array dataflow.  A chunk of codewords whose arrays (8n + 16M bytes each) fit the Infinity Cache decodes
 // all its iterations before the next chunk starts; chunks go round-robin over two streams.  Also here: the parity
-// posteriors formed by the check kernel (IRA_CNPAR) and early termination (IraEs) — DESIGN.md §3.8.
+// posteriors formed by the check kernel and early termination (IraEs) — DESIGN.md §3.8.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -63,19 +63,8 @@ struct IraState {
 };
 static_assert(sizeof(IraState) == 12, "one dwordx3 per check state");
 
-#if IRA_DIAG_S8
-// the states as an array of 8-byte pairs indexed like the 12-byte array (the first two thirds of the buffer)
-__device__ __forceinline__ IraState ira_ld_i(const IraState* __restrict__ base, int64_t i) {
-    const float2 m = reinterpret_cast<const float2*>(base)[i];
-    return IraState{m.x, m.y, __float_as_uint(m.x) & 0x3ffu};
-}
-__device__ __forceinline__ void ira_st_i(IraState* __restrict__ base, int64_t i, const IraState& s) {
-    reinterpret_cast<float2*>(base)[i] = make_float2(s.m1, s.m2 + __uint_as_float(s.meta & 1u));
-}
-#else
 __device__ __forceinline__ IraState ira_ld_i(const IraState* __restrict__ base, int64_t i) { return base[i]; }
 __device__ __forceinline__ void ira_st_i(IraState* __restrict__ base, int64_t i, const IraState& s) { base[i] = s; }
-#endif
 __device__ __forceinline__ IraState ira_ld(const IraState* __restrict__ p) { return *p; }
 
 // c2v of slot `slot` from a check state: the argmin slot gets mag2, every other mag1; sign bit from meta
@@ -96,69 +85,18 @@ __device__ __forceinline__ bool ira_task(int T, int Bc, int& cw, int& task) {
     return cw < Bc;
 }
 
-// IRA_VN_ROT (A/B knob, off): the ascending-order sum by a barrel rotation of the d c2v values (log2 d select stages —
-// which the compiler turns into a compare chain per output, ~150 v_cmp / v_cndmask pairs with s_nop hazard waits
-// per degree-8 task) instead of two masked passes (ira_vn_info)
-#ifndef IRA_VN_ROT
-#define IRA_VN_ROT 0
-#endif
-#ifndef IRA_VN_SCHED
-#define IRA_VN_SCHED 1
-#endif
-#ifndef IRA_CN_SCHED
-#define IRA_CN_SCHED 1
-#endif
-// c'[i] = c[(i + rho) mod D], rho < D, by log2(D) stages of selects (rotations compose additively mod D)
-template <int D>
-__device__ __forceinline__ void rotate_left(float (&c)[D], int rho) {
-    static_for<0, 5>([&](auto BB) __attribute__((always_inline)) {
-        constexpr int sh = 1 << decltype(BB)::value;
-        if constexpr (sh < D) {
-            const bool on = (rho & sh) != 0;
-            float t[D];
-#pragma unroll
-            for (int i = 0; i < D; ++i) t[i] = on ? c[(i + sh) % D] : c[i];
-#pragma unroll
-            for (int i = 0; i < D; ++i) c[i] = t[i];
-        }
-    });
-}
-
 // Workgroup shape: one task at a time over kIraLanes threads (6 waves over the 360 positions; lanes past 360
 // repeat the last position and store nothing), `tpw` tasks one after the other.  Every load of a task is issued
 // before the first is used: a task waits on one memory round trip, not one per edge (A/B
 // profiles/r05/ab/ab_c4_ira_restructure.txt).  Two tasks side by side per workgroup measured no faster
 // (ab_c4_ira_tpp.txt), nor did several positions per lane (ab_c4_ira_ppl.txt).
 constexpr int kIraLanes = 384;
-#ifndef IRA_DIAG_NOPAR
-#define IRA_DIAG_NOPAR 0  // DIAGNOSTIC BUILD ONLY (wrong results): the VN skips its parity tasks, to price them
-#endif
-// IRA_CNPAR: the check kernel forms the posterior of parity p(r, b) itself as soon as it has the new states of rows
+// Fused parity posteriors: the check kernel forms the posterior of parity p(r, b) itself as soon as it has the new states of rows
 // r and r + 1 (consecutive rows of one workgroup: the row loop carries row r's new state to row r + 1), with the
 // variable kernel's operations, (L + c2v_r) + c2v_{r+1}; the variable kernel keeps only the parity rows that end a
 // check workgroup's group (their r + 1 lives in another workgroup) — 15 of 90 for DVB-S2 1/2 at 6 rows per group.
 // The posteriors it writes are the NEXT iteration's, while other check workgroups still read this iteration's: the
 // parity posteriors ping-pong between two buffers (ParBuf), M floats per codeword more.  Bitwise the same.
-#ifndef IRA_DIAG_VN4
-#define IRA_DIAG_VN4 0  // DIAGNOSTIC BUILD ONLY (wrong results): information c2v read as 4 contiguous bytes, to price 12 -> 4
-#endif
-#ifndef IRA_CNPAR
-#define IRA_CNPAR 1
-#endif
-#ifndef IRA_VN_PAIR
-#define IRA_VN_PAIR 0  // variable kernel: two information tasks of one degree with their loads in flight together (A/B knob)
-#endif
-#ifndef IRA_CN_EXACT
-// check kernel instances for at most 5 and 6 information slots: no gathers of padded slots (DVB-S2 1/2 has 5 per check;
-// the MAXR = 8 instance loads 8).  Config [4] 59.0 -> 60.3k cw/s (profiles/r06/ab/ab_c4_ira_r6x.txt)
-#define IRA_CN_EXACT 1
-#endif
-#ifndef IRA_CN_PF
-#define IRA_CN_PF 0  // check kernel: row ra + 1's loads issued before row ra's arithmetic (A/B knob)
-#endif
-#ifndef IRA_DIAG_S8
-#define IRA_DIAG_S8 0  // DIAGNOSTIC BUILD ONLY (wrong results): check states of 8 bytes (m1, m2; meta from m1's bits), to price 12 -> 8
-#endif
 
 // parity posteriors of codeword c, parity index j = r 360 + b: p[c stride + j]
 struct ParBuf {
@@ -204,13 +142,8 @@ __device__ __forceinline__ void ira_vn_load(cint32* row, int64_t vo, int64_t so,
         int b = p + sh;
         in.w[t] = b >= kIZ;
         b -= in.w[t] ? kIZ : 0;
-#if IRA_DIAG_S8
-        (void)Sb;
-        in.st[t] = ira_ld_i(S, so + ra * kIZ + b);
-#else
         const uint32_t off = (uint32_t)(ra * kIZ + b) * (uint32_t)sizeof(IraState);
         in.st[t] = ira_ld(reinterpret_cast<const IraState*>(Sb + off));
-#endif
     });
     in.a = L[vo + p];
 }
@@ -223,62 +156,27 @@ __device__ __forceinline__ void ira_vn_sum(cint32* row, int64_t vo, int pos, flo
         c[t] = ira_c2v(in.st[t], row[t] >> 17);
     });
     float sum = in.a;
-#if IRA_VN_ROT
-    int wrapped = 0;
-#pragma unroll
-    for (int t = 0; t < D; ++t) wrapped += in.w[t];
-    const int rho = wrapped == 0 ? 0 : D - wrapped;
-    rotate_left<D>(c, rho);
-#pragma unroll
-    for (int t = 0; t < D; ++t) sum = sum + c[t];
-#else
 #pragma unroll
     for (int t = 0; t < D; ++t) sum = sum + (in.w[t] ? c[t] : -0.0f);
 #pragma unroll
     for (int t = 0; t < D; ++t) sum = sum + (in.w[t] ? -0.0f : c[t]);
-#endif
     if (pos < kIZ) app[vo + pos] = sum;
 }
 template <int D>
 __device__ __forceinline__ void ira_vn_info(cint32* row, int64_t vo, int64_t so, int pos,
                                             const float* __restrict__ L, const IraState* __restrict__ S,
                                             float* __restrict__ app) {
-#if IRA_DIAG_VN4
-    const int p = min(pos, kIZ - 1);
-    float c[D];
-    bool w[D];
-    const float a = L[vo + p];
-    static_for<0, D>([&](auto TT) __attribute__((always_inline)) {
-        constexpr int t = decltype(TT)::value;
-        const int e = row[t];
-        const int ra = e & 0xff, sh = (e >> 8) & 0x1ff, slot = e >> 17;
-        int b = p + sh;
-        w[t] = b >= kIZ;
-        b -= w[t] ? kIZ : 0;
-        const float x = reinterpret_cast<const float*>(S)[so + (int64_t)ra * kIZ + b];
-        c[t] = ira_c2v(IraState{x, x, (uint32_t)slot << 27}, slot);
-    });
-    float sum = a;
-#pragma unroll
-    for (int t = 0; t < D; ++t) sum = sum + (w[t] ? c[t] : -0.0f);
-#pragma unroll
-    for (int t = 0; t < D; ++t) sum = sum + (w[t] ? -0.0f : c[t]);
-    if (pos < kIZ) app[vo + pos] = sum;
-#else
     VnIn<D> in;
     ira_vn_load<D>(row, vo, so, pos, L, S, in);
-    // IRA_VN_SCHED: every state load issued before the first is consumed (the scheduler had interleaved the first
+    // every state load issued before the first is consumed (the scheduler had interleaved the first
     // loads' decompression with the later loads' issue, behind a wait for the first ones: two round trips per task)
-#if IRA_VN_SCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
     ira_vn_sum<D>(row, vo, pos, app, in);
-#endif
 }
 
 // One task = one variable group (information group g < G, or parity row a = g - G) of one codeword; lanes =
 // the 360 positions.  Writes app in the permuted layout (information: g*360 + m, parity: k + a*360 + b).
-// Parity rows: every row (pgrp = 0), or only the last row of each group of pgrp check rows (IRA_CNPAR: the check
+// Parity rows: every row (pgrp = 0), or only the last row of each group of pgrp check rows (the check
 // kernel formed the others); their posteriors go to `par`.
 template <int MAXDV, bool ES>
 __global__ __launch_bounds__(kIraLanes) void k_ira_vn(IRADev t, const float* __restrict__ L, float* __restrict__ app,
@@ -307,33 +205,13 @@ __global__ __launch_bounds__(kIraLanes) void k_ira_vn(IRADev t, const float* __r
             const int64_t vo = (int64_t)cw * t.n + (int64_t)gi * kIZ;
             const int d = t.vdeg[gi];
             cint32* row = t.vn + gi * kIVS;
-#if IRA_VN_PAIR
-            // two information tasks of one degree: both tasks' loads in flight together
-            const bool two = gi + 1 < gend && gi + 1 < t.G && t.vdeg[gi + 1] == d;
-#endif
             static_for<1, MAXDV + 1>([&](auto DD) __attribute__((always_inline)) {
                 constexpr int D = decltype(DD)::value;
                 if (d == D) {
-#if IRA_VN_PAIR
-                    if (two) {
-                        VnIn<D> i0, i1;
-                        ira_vn_load<D>(row, vo, so, pos, L, S, i0);
-                        ira_vn_load<D>(row + kIVS, vo + kIZ, so, pos, L, S, i1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        ira_vn_sum<D>(row, vo, pos, app, i0);
-                        ira_vn_sum<D>(row + kIVS, vo + kIZ, pos, app, i1);
-                    } else {
-                        ira_vn_info<D>(row, vo, so, pos, L, S, app);
-                    }
-#else
                     ira_vn_info<D>(row, vo, so, pos, L, S, app);
-#endif
                 }
             });
-#if IRA_VN_PAIR
-            gi += two ? 1 : 0;
-#endif
-        } else if (!IRA_DIAG_NOPAR) {
+        } else {
             // parity p_j, j = r + q pos: checks j (its own (r, pos), slot kIPS) and j + 1 (slot kIPS + 1 there)
             const int r = pgrp > 0 ? min((gi - t.G + 1) * pgrp, t.q) - 1 : gi - t.G;
             const int p = min(pos, kIZ - 1);
@@ -347,9 +225,7 @@ __global__ __launch_bounds__(kIraLanes) void k_ira_vn(IRADev t, const float* __r
             const bool has1 = p1 < kIZ;  // j + 1 < M
             const int64_t i1 = so + (int64_t)r1 * kIZ + (has1 ? p1 : 0);
             const IraState s0 = ira_ld_i(S, i0), s1 = ira_ld_i(S, i1);
-#if IRA_VN_SCHED
             __builtin_amdgcn_sched_barrier(0);  // both states and L in flight before the first use
-#endif
             const float c0 = ira_c2v(s0, kIPS);
             const float x1 = ira_c2v(s1, kIPS + 1);
             const float c1 = has1 ? x1 : -0.0f;  // x + (-0) == x bit for bit: the last parity has one check
@@ -360,7 +236,7 @@ __global__ __launch_bounds__(kIraLanes) void k_ira_vn(IRADev t, const float* __r
 
 // One task = one check row a of one codeword; lanes = positions b.  Reads the posteriors of the row's variables
 // and its own state, writes the new state (the oracle's k_cn_ms arithmetic on v2c = app - c2v).
-// Parity posteriors read from `pr`; with FUSE (IRA_CNPAR) the next iteration's parity posteriors of every row but
+// Parity posteriors read from `pr`; with FUSE the next iteration's parity posteriors of every row but
 // the group's last are written to `pw` (the variable kernel forms the rest), from L (`L`) and the new states.
 template <int MAXR, bool FUSE, bool ES>
 __global__ __launch_bounds__(kIraLanes) void k_ira_cn(IRADev t, const float* __restrict__ app, ParBuf pr, ParBuf pw,
@@ -472,29 +348,12 @@ __global__ __launch_bounds__(kIraLanes) void k_ira_cn(IRADev t, const float* __r
             prev = nst;
         }
     };
-#if IRA_CN_PF
-    // software-pipelined: row ra + 1's loads are issued before row ra's arithmetic, so each wave keeps two rows of
-    // loads in flight (the kernel runs about one round of workgroups per launch: the loads in flight per wave, not
-    // the number of waves, set how much of the memory latency is hidden)
-    In cur;
-    fetch(r0, cur);
-    for (int ra = r0; ra < r1; ++ra) {
-        In nxt;
-        if (ra + 1 < r1) fetch(ra + 1, nxt);
-        __builtin_amdgcn_sched_barrier(0);
-        update(ra, cur);
-        cur = nxt;
-    }
-#else
     for (int ra = r0; ra < r1; ++ra) {
         In in;
         fetch(ra, in);
-#if IRA_CN_SCHED
         __builtin_amdgcn_sched_barrier(0);  // the state, both parity posteriors, L and every gather in flight first
-#endif
         update(ra, in);
     }
-#endif
     if constexpr (ES) {  // this group's word (every thread of the workgroup gets here)
         const bool any = __syncthreads_or(unsat || es.it == 0);
         if (threadIdx.x == 0) es.flg[(int64_t)cw * es.ng + tb] = any ? 1 : 0;
@@ -682,7 +541,7 @@ static int64_t ira_chunk(const IRASpec* s, int64_t B, int ns = 1) {
     const char* env = getenv("LDPC_IRA_BUDGET_MB");
     const int64_t budget = ((env ? (int64_t)atol(env) : 240) << 20) / ns;
     if (budget <= 0) return B;
-    const int64_t per = 8 * (int64_t)s->n + 12 * (int64_t)s->M + (IRA_CNPAR ? 4 * (int64_t)s->M : 0);
+    const int64_t per = 8 * (int64_t)s->n + 12 * (int64_t)s->M + 4 * (int64_t)s->M;
     int64_t bc = budget / per / 8 * 8;
     if (bc < 8) bc = 8;
     if (bc >= B) return B;
@@ -703,12 +562,12 @@ static int ira_streams() {
     return v < 1 ? 1 : (v > 4 ? 4 : v);
 }
 
-// L, app, check states, (IRA_CNPAR) the second parity-posterior buffer and the early-stop words (conv, flg: at
+// L, app, check states, the second parity-posterior buffer and the early-stop words (conv, flg: at
 // most q groups) of bc codewords
 static size_t ira_set_bytes(const IRASpec* s, int64_t bc) {
     auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     return 2 * a256((size_t)bc * s->n * 4) + a256((size_t)bc * s->M * sizeof(IraState)) +
-           (IRA_CNPAR ? a256((size_t)bc * s->M * 4) : 0) + a256((size_t)bc * 4 * (1 + s->q));
+           a256((size_t)bc * s->M * 4) + a256((size_t)bc * 4 * (1 + s->q));
 }
 
 size_t ira_workspace(const IRASpec* s, int64_t B, const ldpc_params&) {
@@ -751,13 +610,11 @@ int ira_decode(const IRASpec* s, const float* llr, int64_t B, const ldpc_params&
         float* L = (float*)w;
         float* app = (float*)(w + a256((size_t)bc * s->n * 4));
         IraState* S = (IraState*)(w + 2 * a256((size_t)bc * s->n * 4));
-        // parity posteriors: P[0] in app's parity region, P[1] its own buffer (IRA_CNPAR; otherwise P[0] again)
+        // parity posteriors: P[0] in app's parity region, P[1] its own buffer
         const ParBuf P0{app + s->k, s->n};
-        const ParBuf P1 = IRA_CNPAR ? ParBuf{(float*)(w + 2 * a256((size_t)bc * s->n * 4) +
-                                                      a256((size_t)bc * s->M * sizeof(IraState))), s->M}
-                                    : P0;
+        const ParBuf P1{(float*)(w + 2 * a256((size_t)bc * s->n * 4) + a256((size_t)bc * s->M * sizeof(IraState))), s->M};
         int32_t* esw = (int32_t*)(w + 2 * a256((size_t)bc * s->n * 4) + a256((size_t)bc * s->M * sizeof(IraState)) +
-                                  (IRA_CNPAR ? a256((size_t)bc * s->M * 4) : 0));
+                                  a256((size_t)bc * s->M * 4));
         const bool es_on = (p.flags & LDPC_F_EARLY_STOP) != 0;
         IraEs es{esw, esw + bc, (s->q + tpw - 1) / tpw, 0};
         const int b = (int)(B - o < bc ? B - o : bc);
@@ -773,27 +630,23 @@ int ira_decode(const IRASpec* s, const float* llr, int64_t B, const ldpc_params&
             // VN(it) writes the parity rows the check kernel did not form into P[it & 1] (all of them before the
             // first check pass); CN(it) reads P[it & 1] and forms the next iteration's into P[(it + 1) & 1]
             const ParBuf pv = (it & 1) ? P1 : P0, pn = (it & 1) ? P0 : P1;
-            const int pgrp = (IRA_CNPAR && it > 0) ? tpw : 0;
+            const int pgrp = it > 0 ? tpw : 0;
             const int tv = s->G + (pgrp ? (s->q + pgrp - 1) / pgrp : s->q);
             const unsigned gvn = cw8 * (unsigned)((tv + tpv - 1) / tpv);
             es.it = it;
 #define IRA_VN(D, E) k_ira_vn<D, E><<<gvn, kIraLanes, 0, q>>>(t, L, app, S, pv, pgrp, b, tpv, es)
-#define IRA_CN(R, E) k_ira_cn<R, IRA_CNPAR, E><<<gcn, kIraLanes, 0, q>>>(t, app, pv, pn, L, S, b, p.clamp, p.alpha, p.beta, tpw, es)
+#define IRA_CN(R, E) k_ira_cn<R, true, E><<<gcn, kIraLanes, 0, q>>>(t, app, pv, pn, L, S, b, p.clamp, p.alpha, p.beta, tpw, es)
             if (s->maxdv <= 8) {
                 if (es_on) IRA_VN(8, true); else IRA_VN(8, false);
             } else {
                 if (es_on) IRA_VN(16, true); else IRA_VN(16, false);
             }
             if (it == p.iters) break;  // the last VN pass is the final layer's posterior
-#if IRA_CN_EXACT
             if (s->maxr <= 5) {
                 if (es_on) IRA_CN(5, true); else IRA_CN(5, false);
             } else if (s->maxr <= 6) {
                 if (es_on) IRA_CN(6, true); else IRA_CN(6, false);
             } else if (s->maxr <= 8) {
-#else
-            if (s->maxr <= 8) {
-#endif
                 if (es_on) IRA_CN(8, true); else IRA_CN(8, false);
             } else {
                 if (es_on) IRA_CN(kICS, true); else IRA_CN(kICS, false);

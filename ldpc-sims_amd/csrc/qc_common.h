@@ -155,12 +155,6 @@ constexpr int col_edge(int j, int k) {  // k-th edge of block column j in ascend
 }
 
 // ---- lane rotations (ds_bpermute) shared by the register kernels ----------------------------------
-#ifndef QC_DIAG_DPP
-#define QC_DIAG_DPP 0
-#endif
-#ifndef QC_DIAG_NOSEL
-#define QC_DIAG_NOSEL 0
-#endif
 
 // lanes whose lifting index z lies in [lo, hi), in each codeword's lane group
 template <int Z, int CPW>
@@ -179,15 +173,12 @@ constexpr uint64_t lane_range_mask(int lo, int hi) {
 // the idle lanes 54..63 of Z = 54 sit in the upper half; aliased to lifting index z - Z (round 2) they read
 // lanes just above 0..9's sources — a distinct address on a bank the wrapped active lanes use, exactly one
 // extra cycle per rotation on every (1296,2/3) rotation (modelled: 104 of 104; measured SQ_LDS_BANK_CONFLICT
-// = SQ_INSTS_LDS).  QC_IDLE_ALIAS: alias them to an active lane of the SAME half instead (z' = 32 + (z - Z)
+// = SQ_INSTS_LDS).  They alias to an active lane of the SAME half instead (z' = 32 + (z - Z)
 // mod (Z - 32)), wrap decision included, so they repeat its address exactly: 0.62 extra cycles per rotation
 // (the rest are the active lanes' own wrap collisions).  CPW == 2 (Z <= 32) is conflict-free either way.
-#ifndef QC_IDLE_ALIAS
-#define QC_IDLE_ALIAS 1
-#endif
 template <int Z, int CPW>
 constexpr int idle_alias(int z) {  // z >= Z: the lifting index whose rotation addresses this idle lane repeats
-    if constexpr (QC_IDLE_ALIAS && CPW == 1 && Z > 32) return 32 + (z - Z) % (Z - 32);
+    if constexpr (CPW == 1 && Z > 32) return 32 + (z - Z) % (Z - 32);
     else return z - Z;
 }
 template <int Z, int CPW>
@@ -219,28 +210,16 @@ constexpr uint64_t wrap_mask(int lo) {
 // checks the built code for 64-bit SALU moves of high-bit literals.
 template <uint64_t MASK>
 __device__ __forceinline__ int sel_lanes(int a, int b) {
-#if QC_DIAG_NOSEL
-    (void)b;  // DIAGNOSTIC BUILD ONLY (wrong results): no wrap select, to price the address selects
-    return a;
-#else
     int r;
     if constexpr ((MASK >> 31) == 0x1FFFFFFFFull)
         asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(~MASK));
     else
         asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(MASK));
     return r;
-#endif
 }
 
 __device__ __forceinline__ float bperm(int addr, float v) {
-#if QC_DIAG_DPP
-    // DIAGNOSTIC BUILD ONLY (wrong results): a VALU DPP move instead of the LDS-pipe permute, to price
-    // the ds_bpermute traffic.  The address stays live so its computation is still timed.
-    asm volatile("" ::"v"(addr));
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x121, 0xf, 0xf, false));
-#else
     return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
-#endif
 }
 
 // Lane-mask rotation for the early-stop syndrome: bit i of the result = bit (i + S) mod Z of x, in each

@@ -15,7 +15,7 @@
 //     rotation per edge per sweep, where the flooding kernels rotate twice (gather, scatter).
 //   * no rotation at either end: L_j is loaded from global memory in the frame of the column's LAST row and
 //     the outputs are stored from that same frame, which every sweep ends in — whatever `iters` is.
-//   * the check state never rotates.  Fixed count: one c2v register per edge (QC_LAY_STORED, measured faster).
+//   * the check state never rotates.  Fixed count: one c2v register per edge (STORED, measured faster).
 //     Early stop: compressed per base row, the two post-normalisation magnitudes M1 = mag(min1),
 //     M2 = mag(min2) and one word with the argmin slot and the sign of every c2v (3 VGPRs per base row); the
 //     previous c2v[e] is (slot == argmin ? M2 : M1) with its sign bit, the bits of a stored message.
@@ -35,19 +35,8 @@ namespace ldpc {
 #define QC_LAY_WAVES_PER_SIMD_EARLY 4  // spill-free at 86-99 VGPRs; bounded to 96 by 5 waves the (648,1/2) kernels
                                        // spill 4 VGPRs (the all-rows syndrome's 64-bit masks overflow the SGPRs)
 #endif
-#ifndef QC_LAY_LDSROT
-#define QC_LAY_LDSROT 1  // fixed count, Z <= 32: rotations through the wave's LDS row (0: ds_bpermute)
-#endif
 #ifndef QC_LAY_TPB_EARLY
 #define QC_LAY_TPB_EARLY 64  // early stop: one-wave workgroups leave the CU as they finish (as QC_ST_TPB_EARLY)
-#endif
-#ifndef QC_LAY_STORED
-// Fixed count: one c2v register per edge (check frame, never rotated) instead of the compressed row state — no
-// reconstruction of the old message and no sign / argmin packing, ~10 instead of ~15 VALU instructions per edge
-// in a kernel bound by VALU issue: A/B on (648,1/2), 25 sweeps, B = 65,536: 1.544 -> 0.848 ms per launch
-// (profiles/layered/), at 119-121 VGPRs (4 waves) instead of 59-69 (7 waves).  Early stop keeps the compressed
-// state: with 88 more registers its all-rows syndrome spills.
-#define QC_LAY_STORED 1
 #endif
 template <bool EARLY>
 constexpr int lay_tpb() { return EARLY ? QC_LAY_TPB_EARLY : 256; }
@@ -90,7 +79,12 @@ __global__ __launch_bounds__(256, EARLY ? QC_LAY_WAVES_PER_SIMD_EARLY : QC_LAY_W
     static_assert(Z <= 64, "register kernel needs Z <= 64");
     static_assert(C::MAXDC <= 27, "slot signs and the argmin share one word");
     constexpr int CPW = (Z <= 32) ? 2 : 1;
-    constexpr bool STORED = QC_LAY_STORED && !EARLY;
+    // Fixed count: one c2v register per edge (check frame, never rotated) instead of the compressed row state — no
+    // reconstruction of the old message and no sign / argmin packing, ~10 instead of ~15 VALU instructions per edge
+    // in a kernel bound by VALU issue: A/B on (648,1/2), 25 sweeps, B = 65,536: 1.544 -> 0.848 ms per launch
+    // (profiles/layered/), at 119-121 VGPRs (4 waves) instead of 59-69 (7 waves).  Early stop keeps the compressed
+    // state: with 88 more registers its all-rows syndrome spills.
+    constexpr bool STORED = !EARLY;
     using F = LayFrames<C>;
     const int lane = threadIdx.x & 63;
     const int half = (CPW == 2) ? (lane >> 5) : 0;
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(256, EARLY ? QC_LAY_WAVES_PER_SIMD_EARLY : QC_LAY_W
     const int zb = lane_zb<Z, CPW>(z);
     const int base4 = (half * 32 + zb) * 4;
     const int base4m = base4 - 4 * Z;
-    constexpr bool LDSROT = QC_LAY_LDSROT && !EARLY && Z <= 32;
+    constexpr bool LDSROT = !EARLY && Z <= 32;
     __shared__ float Rw[LDSROT ? lay_tpb<EARLY>() : 1];  // one 64-lane rotation row per wave
     const int wrow = LDSROT ? (int)(threadIdx.x & ~63u) * 4 : 0;
     const int rb4 = base4 + wrow, rb4m = base4m + wrow;

@@ -28,27 +28,14 @@
 
 namespace ldpc {
 
-// QC_PK_LDSROT(_EARLY): lane rotations through a per-wave LDS row instead of ds_bpermute (as qc.hip's
-// QC_PH_LDSROT).  Off: this kernel is not bound by the LDS pipe — A/B 1-3 % slower in every configuration
+// QC_PK_LDSROT(_EARLY): lane rotations through a per-wave LDS row instead of ds_bpermute (as k_qc_ms_ph's,
+// qc_ms.h).  Off: this kernel is not bound by the LDS pipe — A/B 1-3 % slower in every configuration
 // ((1296,2/3) 20 it fixed 50.5 vs 49.8, early stop 49.1 vs 48.4; (648,1/2) 103 vs 102, 101 vs 98 M cw/s).
 #ifndef QC_PK_LDSROT
 #define QC_PK_LDSROT 0
 #endif
 #ifndef QC_PK_LDSROT_EARLY
 #define QC_PK_LDSROT_EARLY 0
-#endif
-// QC_PK_DROT(_EARLY): lane rotations through a per-wave DOUBLED LDS row: every active lane stores its value at
-// slots z and z + Z of its lane group's row with one ds_write2_b32, and reads slot z + rho (< 2Z: no wrap, so no
-// per-rotation address select and no address registers — the offset is the ds immediate); idle lanes write and
-// read a private dummy stretch.  A wave's LDS operations run in order, so the row needs no barrier.  Bitwise the
-// same results (every packed / quantized parity test passes on it) with 84 fewer VALU per wave-iteration, but
-// slower: config [3] 67.3 -> 62.1 M cw/s, fixed count 53.5 -> 50.8, (648,1/2) early stop 114.7 -> 107.9 (A/B
-// profiles/r04/ab/ab_drot.txt) — a rotation's store-then-load round trip sits on the chain ds_bpermute shortens.
-#ifndef QC_PK_DROT
-#define QC_PK_DROT 0
-#endif
-#ifndef QC_PK_DROT_EARLY
-#define QC_PK_DROT_EARLY 0
 #endif
 #ifndef QC_PK_WAVES_PER_SIMD
 #define QC_PK_WAVES_PER_SIMD 4
@@ -62,21 +49,8 @@ namespace ldpc {
 #ifndef QC_PK_ADDR_MIN_USES_Z64
 #define QC_PK_ADDR_MIN_USES_Z64 4  // Z > 32 (one lane group): 6 address registers at 4 uses (18 at 3)
 #endif
-#ifndef QC_PK_ES_ROWS
-#define QC_PK_ES_ROWS 1  // early-stop syndrome row by row with an early exit (one codeword pair per wave, Z = 54)
-#endif
 #ifndef QC_PK_MASK_IDLE
 #define QC_PK_MASK_IDLE 0  // A/B -2 % on config [3] (profiles/r04/ab/ab_mask.txt)
-#endif
-#ifndef QC_PK_DIAG
-// DIAGNOSTIC BUILDS ONLY (wrong results; DESIGN.md §3.3, scripts/pk_floor_diag.sh): 1 = no bit stores, 2 = no
-// LLR loads — prices the per-launch data movement
-#define QC_PK_DIAG 0
-#endif
-#ifndef QC_PK_PRIO
-// 1: s_setprio 1 over the VN phase (0 over the CN phase), early stop and fixed count: config [3] 66.9 -> 67.5 M
-// cw/s (A/B profiles/r04/ab/ab_prio.txt); 2: the reverse (-1.3 %)
-#define QC_PK_PRIO 1
 #endif
 #ifndef QC_PK_TPB
 #define QC_PK_TPB 256
@@ -163,34 +137,23 @@ constexpr int min_row_deg() {
 __device__ __forceinline__ uint32_t pmin3(uint32_t a, uint32_t b, uint32_t c) {
     return as_u(__builtin_elementwise_minimum(__builtin_elementwise_minimum(as_h2(a), as_h2(b)), as_h2(c)));
 }
-#ifndef QC_PK_MIN3
-#define QC_PK_MIN3 1  // two-minimum over edge pairs with v_pk_minimum3_f16: 5 VALU per 2 edges instead of 6
-#endif
-// the two smallest of D packed non-negative magnitudes (each result is one of the inputs, bit for bit).
-// QC_PK_MIN3, per pair (x, y) with lo/hi = min/max(x, y): the new second minimum of {mn1 <= mn2, x, y} is
+// the two smallest of D packed non-negative magnitudes (each result is one of the inputs, bit for bit), over edge
+// pairs with v_pk_minimum3_f16 (5 VALU per 2 edges instead of 6): per pair (x, y) with lo/hi = min/max(x, y): the new second minimum of {mn1 <= mn2, x, y} is
 // min(mn2, hi, max(mn1, lo)) (lo < mn1: min(mn1, hi); else min(mn2, lo)), the new minimum min(mn1, lo).
 template <int D>
 __device__ __forceinline__ void two_min_pk(const uint32_t (&a)[D], uint32_t& mn1, uint32_t& mn2) {
     static_assert(D >= 2, "packed min-sum: check degree >= 2");
     mn1 = pmin(a[0], a[1]);
     mn2 = pmax(a[0], a[1]);
-    if constexpr (QC_PK_MIN3) {
-        static_for<0, (D - 2) / 2>([&](auto pp) __attribute__((always_inline)) {
-            constexpr int t = 2 + 2 * decltype(pp)::value;
-            const uint32_t lo = pmin(a[t], a[t + 1]), hi = pmax(a[t], a[t + 1]);
-            mn2 = pmin3(mn2, hi, pmax(mn1, lo));
-            mn1 = pmin(mn1, lo);
-        });
-        if constexpr (D % 2 == 1) {
-            mn2 = pmin(mn2, pmax(mn1, a[D - 1]));
-            mn1 = pmin(mn1, a[D - 1]);
-        }
-    } else {
-        static_for<2, D>([&](auto tt) __attribute__((always_inline)) {
-            constexpr int t = decltype(tt)::value;
-            mn2 = pmin(mn2, pmax(mn1, a[t]));
-            mn1 = pmin(mn1, a[t]);
-        });
+    static_for<0, (D - 2) / 2>([&](auto pp) __attribute__((always_inline)) {
+        constexpr int t = 2 + 2 * decltype(pp)::value;
+        const uint32_t lo = pmin(a[t], a[t + 1]), hi = pmax(a[t], a[t + 1]);
+        mn2 = pmin3(mn2, hi, pmax(mn1, lo));
+        mn1 = pmin(mn1, lo);
+    });
+    if constexpr (D % 2 == 1) {
+        mn2 = pmin(mn2, pmax(mn1, a[D - 1]));
+        mn1 = pmin(mn1, a[D - 1]);
     }
 }
 
@@ -205,18 +168,11 @@ __device__ __forceinline__ uint32_t xor_all_u(const uint32_t (&v)[D]) {
     return t;
 }
 
-// QC_PK_PAIRS (A/B knob, early stop; default 1): each wave decodes this many codeword pairs one after the other,
-// the body straight-line per pair (no runtime loop around it: round 5's persistent loop had raised the register
-// demand past the 3-waves/SIMD budget), wave w taking pairs w, w + W, ... (W = the grid's waves)
-#ifndef QC_PK_PAIRS
-#define QC_PK_PAIRS 1
-#endif
 template <class C, bool EARLY, bool BETA>
 __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restrict__ llr, int64_t B, int iters, float qmax,
                                             float app_max, float beta, float qinv, int flags, uint8_t* __restrict__ bits,
-                                            float* __restrict__ soft, int32_t* __restrict__ iters_used, int64_t pair_off) {
-    // the work-item id through an empty asm: every lane-derived value is recomputed per pair (QC_PK_PAIRS > 1)
-    // rather than kept live from one pair's body into the next
+                                            float* __restrict__ soft, int32_t* __restrict__ iters_used) {
+    // the work-item id through an empty asm: the lane-derived values come from it, not from threadIdx.x
     unsigned tx = threadIdx.x;
     asm volatile("" : "+v"(tx));
     constexpr int Z = C::Z, NB = C::NB, MB = C::MB, N = NB * Z;
@@ -226,8 +182,7 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
     static_assert(min_row_deg<C>() >= 2, "check degree >= 2");
     constexpr int CPW = (Z <= 32) ? 2 : 1;
     constexpr bool LDSROT = EARLY ? QC_PK_LDSROT_EARLY : QC_PK_LDSROT;
-    constexpr bool DROT = EARLY ? QC_PK_DROT_EARLY : QC_PK_DROT;
-    constexpr bool ILV = QC_PK_ILV && CPW == 1 && Z % 2 == 0 && !LDSROT && !DROT;
+    constexpr bool ILV = QC_PK_ILV && CPW == 1 && Z % 2 == 0 && !LDSROT;
     const int lane = tx & 63;
     const int half = (CPW == 2) ? (lane >> 5) : 0;
     // lifting index of this lane (>= Z: idle); ILV: even z in the lower half, odd in the upper
@@ -245,7 +200,7 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
     const int lrow = tx * LSTR;
     const int lrow4 = lrow * 4;  // bytes (lds_reload)
 
-    // lane rotations through a per-wave LDS row (as k_qc_ms_ph, qc.hip QC_PH_LDSROT) or ds_bpermute
+    // lane rotations through a per-wave LDS row (as k_qc_ms_ph, qc_ms.h) or ds_bpermute
     __shared__ uint32_t Rw[LDSROT ? pk_tpb<EARLY>() : 1];
     const int wrow = LDSROT ? (int)(tx & ~63u) * 4 : 0;
     const int rb4 = base4 + wrow, rb4m = base4m + wrow;
@@ -276,21 +231,12 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
     int ra[Z];
     static_for<1, Z>([&](auto rr) __attribute__((always_inline)) {
         constexpr int rho = decltype(rr)::value;
-        if constexpr (rot_uses<C>(rho) >= MINU && !DROT) ra[rho] = raddr(rr);
+        if constexpr (rot_uses<C>(rho) >= MINU) ra[rho] = raddr(rr);
     });
-    constexpr int DW = CPW * 2 * Z + 64 + 2 * Z;  // words per wave: doubled rows, then the idle lanes' stretch
-    __shared__ uint32_t Rd[DROT ? (pk_tpb<EARLY>() / 64) * DW : 1];
-    const int da = DROT ? 4 * ((int)(tx >> 6) * DW + ((z < Z) ? half * 2 * Z + z : CPW * 2 * Z + lane)) : 0;
     auto rot = [&](auto rr, uint32_t x) __attribute__((always_inline)) {  // value of lane (z + rho) mod Z
         constexpr int rho = decltype(rr)::value;
         if constexpr (rho == 0) {
             return x;
-        } else if constexpr (DROT) {
-            static_assert(4 * Z <= 255 * 4, "ds_write2 offset1 is 8 bits (in dwords)");
-            asm volatile("ds_write2_b32 %0, %1, %1 offset1:%2" ::"v"((unsigned)(uintptr_t)&Rd[0] + (unsigned)da), "v"(x),
-                         "i"(Z)
-                         : "memory");
-            return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(Rd) + da + 4 * rho);
         } else if constexpr (rot_uses<C>(rho) >= MINU) {
             return xfer(ra[rho], x);
         } else {
@@ -314,14 +260,8 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
             int t = z + C::PHI[j];
             t -= (t >= Z) ? Z : 0;
             const int64_t o = (int64_t)j * Z + t;
-#if QC_PK_DIAG == 2  // DIAGNOSTIC BUILD ONLY (wrong results): no LLR loads, to price them
-            const float x0 = v0 ? (float)((z * 7 + j) % 9) - 4.0f : 0.0f;
-            const float x1 = v1 ? (float)((z * 5 + j) % 9) - 4.0f : 0.0f;
-            (void)o;
-#else
             const float x0 = v0 ? llr[cw0 * N + o] : 0.0f;
             const float x1 = v1 ? llr[(cw0 + 1) * N + o] : 0.0f;
-#endif
             const float q0 = fminf(fmaxf(rintf(x0 * qinv), -qmax), qmax);
             const float q1 = fminf(fmaxf(rintf(x1 * qinv), -qmax), qmax);
             L[j] = pk2(-q0, -q1);
@@ -401,16 +341,15 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
     _Float16* Lh = reinterpret_cast<_Float16*>(Ls);
 
     int it = 0;
-    // QC_PK_MASK_IDLE: idle lanes (z >= Z) sit the iteration loop out, EXEC-masked (as qc.hip QC_PH_MASK_IDLE); the
+    // QC_PK_MASK_IDLE: idle lanes (z >= Z) sit the iteration loop out, EXEC-masked (as k_qc_ms_ph, qc_ms.h); the
     // early-stop decisions come from ballots restricted to the active lanes, so they are unchanged
     const bool loop_lane = !QC_PK_MASK_IDLE || z < Z;
     if (loop_lane)
     for (; it + 1 < iters; ++it) {
-        if constexpr (QC_PK_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if constexpr (QC_PK_PRIO == 2) __builtin_amdgcn_s_setprio(1);
+        // s_setprio 1 over the VN phase, 0 over the CN phase: config [3] 66.9 -> 67.5 M cw/s (A/B profiles/r04/ab/ab_prio.txt)
+        __builtin_amdgcn_s_setprio(0);
         cn_phase();
-        if constexpr (QC_PK_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-        if constexpr (QC_PK_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(1);
         if constexpr (EARLY) {
             uint32_t app[NB];
             static_for<0, NB>([&](auto pp) __attribute__((always_inline)) {
@@ -421,7 +360,7 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
             // every check.  Per block column one ballot of the hard decisions (oracle: bit = APP < 0) per half,
             // rotated into the frame of each row it touches and XOR-ed there.
             uint32_t conv;
-            if constexpr (QC_PK_ES_ROWS && CPW == 1) {
+            if constexpr (CPW == 1) {
                 // Row by row with an early exit (one codeword pair per wave, (1296,2/3)): `conv` starts as the
                 // codewords not yet done and loses each one whose row parity is nonzero; the scan stops once no
                 // codeword of the wave can still be satisfied — at low Eb/N0 after the first row, so the test
@@ -502,7 +441,7 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
     const int zo = ILV ? ((tid & 31) < Z / 2 ? 2 * (tid & 31) + ((tid >> 5) & 1) : Z + (tid & 31))
                        : ((CPW == 2) ? (tid & 31) : (tid & 63));
     const int go = (CPW == 2) ? ((tid >> 5) & 1) : 0;
-    const int64_t c0 = (((((int64_t)blockIdx.x * blockDim.x + tid) >> 6) + pair_off) * CPW + go) * 2;
+    const int64_t c0 = (((((int64_t)blockIdx.x * blockDim.x + tid) >> 6)) * CPW + go) * 2;
     const bool park0 = EARLY && ((done >> (2 * go)) & 1u), park1 = EARLY && ((done >> (2 * go + 1)) & 1u);
     const bool ok0 = zo < Z && c0 < B, ok1 = zo < Z && c0 + 1 < B;
     static_for<0, NB>([&](auto pp) __attribute__((always_inline)) {
@@ -522,7 +461,7 @@ __device__ __forceinline__ void qms_pk_pair(int64_t wave, const float* __restric
             if (k == 0 ? ok0 : ok1) {
                 const int64_t oo = (c0 + k) * N + o;
                 const float zz = 0.5f * (float)hv[k];
-                if (bits && QC_PK_DIAG != 1) bits[oo] = (uint8_t)(zz <= kZthrF32);  // DIAG 1: no output, to price it
+                if (bits) bits[oo] = (uint8_t)(zz <= kZthrF32);
                 if (soft) soft[oo] = (flags & LDPC_F_SOFT_Z) ? zz : 1.0f - 1.0f / (1.0f + expf(-zz));
             }
         }
@@ -537,14 +476,8 @@ template <class C, bool EARLY, bool BETA>
 __global__ __launch_bounds__(QC_PK_TPB, EARLY ? QC_PK_WAVES_PER_SIMD_EARLY : QC_PK_WAVES_PER_SIMD) void k_qc_qms_pk(
     const float* __restrict__ llr, int64_t B, int iters, float qmax, float app_max, float beta, float qinv, int flags,
     uint8_t* __restrict__ bits, float* __restrict__ soft, int32_t* __restrict__ iters_used) {
-    constexpr int P = EARLY ? QC_PK_PAIRS : 1;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t W = (int64_t)gridDim.x * (blockDim.x >> 6);
-    static_for<0, P>([&](auto kk) __attribute__((always_inline)) {
-        constexpr int k = decltype(kk)::value;
-        qms_pk_pair<C, EARLY, BETA>(wave + k * W, llr, B, iters, qmax, app_max, beta, qinv, flags, bits, soft, iters_used,
-                                    k * W);
-    });
+    qms_pk_pair<C, EARLY, BETA>(wave, llr, B, iters, qmax, app_max, beta, qinv, flags, bits, soft, iters_used);
 }
 
 template <class C>
@@ -552,7 +485,7 @@ static int launch_qms_pk(const void* llr, int64_t B, const ldpc_params& p, uint8
                          hipStream_t st) {
     constexpr int CPW = (C::Z <= 32) ? 2 : 1;
     const bool es = (p.flags & LDPC_F_EARLY_STOP) != 0;
-    const int64_t waves = ((B + 2 * CPW - 1) / (2 * CPW) + (es ? QC_PK_PAIRS : 1) - 1) / (es ? QC_PK_PAIRS : 1);
+    const int64_t waves = (B + 2 * CPW - 1) / (2 * CPW);
     const float qm = (float)p.qmax, am = (float)p.app_max, b = p.beta, qi = 1.0f / p.qstep;
     const int tpb = es ? pk_tpb<true>() : pk_tpb<false>();
     const unsigned blocks = (unsigned)((waves + tpb / 64 - 1) / (tpb / 64));

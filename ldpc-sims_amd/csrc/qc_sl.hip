@@ -39,7 +39,7 @@ void k_qc_ms_sl(const float* __restrict__ llr, int64_t B, int iters, float clamp
     const int64_t cw = (int64_t)blockIdx.x * 2 + h;
     const bool live = l < ZL;
     const bool valid = live && cw < B;
-    const int zc = live ? l + ZL * k : (QC_SL_IDLE_ALIAS ? ZL * k : 0);  // idle lanes: see qc_sl_sp.h
+    const int zc = live ? l + ZL * k : ZL * k;  // idle lanes: see qc_sl_sp.h
     const int xb = h * 2 * Z + zc;
     float Lr[NB], app[NB];
     {
@@ -180,24 +180,12 @@ static int launch_sl(const void* llr, int64_t B, const ldpc_params& p, uint8_t* 
         if (es) {
             static_assert(std::is_same_v<C, Wifi1944_56>, "one sliced code");
             qc_launch_sp_sl_es_wifi1944_56(x, B, p, bits, sf, used, st);
-        } else if (QC_SL_SP_RS) {  // the plain pass, then the a == 1 rule's pass for units with a zero LLR
-            hipStream_t s2 = st;
-            if (QC_SP_FIXZ) {
-                if (const int rc = qc_sp_fork(x, B, C::NB * C::Z, 2, st, &s2)) return rc;
-                k_qc_sp_rs<C, 2><<<qc_sp_pass2_grid(blocks), tb, 0, s2>>>(x, B, p.iters, p.clamp, p.flags, bits, sf, used, qc_sp_zlist());
-            }
-            k_qc_sp_rs<C, QC_SP_FIXZ ? 1 : 0><<<blocks, tb, 0, st>>>(x, B, p.iters, p.clamp, p.flags, bits, sf, used, qc_sp_zlist());
-            if (QC_SP_FIXZ)
-                if (const int rc = qc_sp_join(st)) return rc;
-        } else {
-            hipStream_t s2 = st;
-            if (QC_SP_FIXZ) {
-                if (const int rc = qc_sp_fork(x, B, C::NB * C::Z, 2, st, &s2)) return rc;
-                k_qc_sp_sl<C, false, 2><<<qc_sp_pass2_grid(blocks), tb, 0, s2>>>(x, B, p.iters, p.clamp, p.flags, bits, sf, used, qc_sp_zlist());
-            }
-            k_qc_sp_sl<C, false, QC_SP_FIXZ ? 1 : 0><<<blocks, tb, 0, st>>>(x, B, p.iters, p.clamp, p.flags, bits, sf, used, qc_sp_zlist());
-            if (QC_SP_FIXZ)
-                if (const int rc = qc_sp_join(st)) return rc;
+        } else {  // the plain pass, and beside it the a == 1 rule's pass for units with a zero LLR
+            hipStream_t s2;
+            if (const int rc = qc_sp_fork(x, B, C::NB * C::Z, 2, st, &s2)) return rc;
+            k_qc_sp_rs<C, 2><<<qc_sp_pass2_grid(blocks), tb, 0, s2>>>(x, B, p.iters, p.clamp, p.flags, bits, sf, used, qc_sp_zlist());
+            k_qc_sp_rs<C, 1><<<blocks, tb, 0, st>>>(x, B, p.iters, p.clamp, p.flags, bits, sf, used, qc_sp_zlist());
+            if (const int rc = qc_sp_join(st)) return rc;
         }
     } else if (p.algo == LDPC_ALGO_QMIN_SUM) {
         const float qm = (float)p.qmax, am = (float)p.app_max, b = (float)(int)p.beta, qi = 1.0f / p.qstep;

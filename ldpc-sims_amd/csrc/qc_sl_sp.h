@@ -44,56 +44,18 @@ constexpr int nz_max() {
 // gather's positions) and the unit's waves pool one ballot per (slot, codeword) in LDS.  A codeword whose
 // syndrome is zero writes its outputs from z_it right there (iters_used = it) and is skipped at the end;
 // the unit leaves the loop when both of its codewords are done.  Bitwise equal to the generic path.
-// QC_SL_SP_SERIAL_CN = k > 0: every k-th edge's exclusive product (CN) / sum (VN) chain starts after the previous edge's
+// Serial chains: every edge's exclusive product (CN) / sum (VN) chain starts after the previous edge's
 // log / tanh output (an empty asm ties them), so one chain is in flight instead of a row's 20 partial
 // products held in registers: 195 -> 112 VGPRs for the same operations in the same order.
-// QC_SL_SP_COMPACT: one exchange buffer for v2c and c2v (a third barrier per row instead of a second
-// buffer).  QC_SL_SP_L: where L lives — 0 VGPRs, 1 LDS, 2 re-read from global memory (an L2 hit) at every
-// use.  Fixed-count kernel: one buffer + L in global = 26 KB of LDS per unit, 112 VGPRs: five units
+// CMP: one exchange buffer for v2c and c2v (a third barrier per row instead of a second
+// buffer).  LM: where L lives — 0 VGPRs, 1 LDS, 2 re-read from global memory (an L2 hit) at every
+// use.  (Only EARLY is instantiated now: two buffers, L in VGPRs; fixed count runs k_qc_sp_rs below.  Freezing CMP /
+// LM at those values changed the register assignment of the built kernel, so the fixed-count form is still here.)
+// Fixed-count kernel: one buffer + L in global = 26 KB of LDS per unit, 112 VGPRs: five units
 // (15 waves) per CU instead of two.
-#ifndef QC_SL_POS_STRIDE
-// lane l of slot wave k holds frame position S*l + k (1) instead of l + ZL*k (0): a rotation by c reads positions
-// (S*l + k + c) mod Z = S*((l + q) mod ZL) + r, whose LDS banks (a/4 mod 32) are distinct for odd S, so no access
-// of the rotated-circulant slots conflicts; with contiguous positions every window that wraps past Z conflicted
-// (round 4: SQ_LDS_BANK_CONFLICT 21 % of the resident kernel's LDS cycles).  A relabelling: bitwise the same.
-#define QC_SL_POS_STRIDE 1
-#endif
-#ifndef QC_SL_IDLE_ALIAS
-#define QC_SL_IDLE_ALIAS 1  // idle lanes read at their wave's first position (0: at position 0, round 2)
-#endif
-#ifndef QC_SL_SP_SERIAL_CN
-#define QC_SL_SP_SERIAL_CN 1
-#endif
-#ifndef QC_SL_SP_SERIAL_ROW
-#define QC_SL_SP_SERIAL_ROW QC_SL_SP_SERIAL_CN  // the check rows' ties alone (cn_ds_row's SERIAL)
-#endif
-#ifndef QC_SL_SP_COMPACT
-#define QC_SL_SP_COMPACT 1
-#endif
-#ifndef QC_SL_SP_COMPACT_EARLY
-#define QC_SL_SP_COMPACT_EARLY 0
-#endif
-#ifndef QC_SL_SP_L
-#define QC_SL_SP_L 2
-#endif
-#ifndef QC_SL_SP_L_EARLY
-#define QC_SL_SP_L_EARLY 0
-#endif
-// QC_SL_SP_LPF (L from global memory): the VN phase loads L of column j + 1 before column j's chains.  The
-// serial-chain asm statements order memory operations, so without it every column waits out an L2 hit.
-#ifndef QC_SL_SP_LPF
-#define QC_SL_SP_LPF 0  // A/B: 1.874 vs 1.887 M cw/s, -0.8 % (profiles/r02/ab/ab_lpf.txt): the other waves hide it
-#endif
-
-#ifndef QC_SL_DIAG_NOBAR
-#define QC_SL_DIAG_NOBAR 0  // DIAGNOSTIC BUILD ONLY (wrong results): no row-exchange barriers, to price them
-#endif
-__device__ __forceinline__ void sl_barrier() {
-    if constexpr (!QC_SL_DIAG_NOBAR) __syncthreads();
-}
 
 // PASS: as k_qc_sp_st's (qc.hip) — 1 = the plain loop for the units k_sp_zero_scan did not list, 2 = the a == 1
-// rule's loop for the listed units, 0 = the plain loop for every unit.  A unit = one workgroup's two codewords;
+// rule's loop for the listed units.  A unit = one workgroup's two codewords;
 // unit_listed is the unit of PASS 2 (the others use the block index).
 template <class C, bool EARLY, int PASS>
 __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float* __restrict__ llr, int64_t B, int iters,
@@ -107,8 +69,8 @@ __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float*
     constexpr int Z = C::Z, S = C::S, ZL = Z / S, NB = C::NB, MB = C::MB, N = NB * Z;
     constexpr int NE = edge_off<C>(MB), NT = nz_max<C>(), ROW = 2 * 2 * Z;  // floats per exchanged circulant
     static_assert(S > 1 && Z % S == 0 && ZL <= 32, "sliced kernel: Z = S * ZL, ZL <= 32");
-    constexpr bool CMP = EARLY ? QC_SL_SP_COMPACT_EARLY : QC_SL_SP_COMPACT;
-    constexpr int LM = EARLY ? QC_SL_SP_L_EARLY : QC_SL_SP_L;
+    constexpr bool CMP = !EARLY;
+    constexpr int LM = EARLY ? 0 : 2;
     __shared__ float Xv[NT * ROW], Xc2[CMP ? 1 : NT * ROW];
     float* const Xc = CMP ? Xv : Xc2;
     __shared__ float Lsh[LM == 1 ? 2 * NB * Z : 1];  // L of both codewords: [half][j][position]
@@ -121,8 +83,7 @@ __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float*
     // served per 32-lane half with bank = (address / 4) mod 32, and aliased to position 0 (round 2) the idle
     // lanes of waves k = 1, 2 read a distinct address on a bank their active lanes use — one extra LDS cycle
     // per read; repeating an active lane's address of their own wave is a broadcast instead.
-    const int p0 = QC_SL_POS_STRIDE ? k : ZL * k;  // this wave's first position
-    const int zc = live ? (QC_SL_POS_STRIDE ? S * l + k : l + ZL * k) : (QC_SL_IDLE_ALIAS ? p0 : 0);
+    const int zc = live ? S * l + k : k;     // idle lanes: this wave's first position
     const int xb = h * 2 * Z + zc;           // this lane's position in an exchange row
     // L = -llr (bp.py:47) of this lane's variable in every block column
     const float* const lp = llr + (valid ? cw * N : 0);
@@ -249,21 +210,17 @@ __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float*
             }
         }
         // VC + tanh in the variable frame (as k_qc_sp_st)
-        constexpr bool LPF = LM == 2 && QC_SL_SP_LPF;
-        float Lnext = LPF ? Lr_at(0) : 0.0f;
         static_for<0, NB>([&](auto jj) __attribute__((always_inline)) {
             constexpr int j = decltype(jj)::value;
             constexpr int dj = col_deg<C>(j);
-            const float Lj = LPF ? Lnext : Lr_at(j);
-            if constexpr (LPF && j + 1 < NB) Lnext = Lr_at(j + 1);  // in flight during this column's chains
-            vn_excl_sums<dj, QC_SL_SP_SERIAL_CN>(  // O(d) exclusive sums (common.h), k chains in flight
+            const float Lj = Lr_at(j);
+            vn_excl_sums<dj, 1>(  // O(d) exclusive sums (common.h), one chain in flight
                 [&](auto kk) __attribute__((always_inline)) { return msg[col_edge<C>(j, decltype(kk)::value)]; },
                 [&](auto kk, float Ssum) __attribute__((always_inline)) {
                     constexpr int q = decltype(kk)::value;
                     constexpr int e = col_edge<C>(j, q);
                     msg[e] = vn_signed_a(sp_vn_arg(Lj, Ssum));  // the (D, S) form's VC output (common.h)
-                    if constexpr (QC_SL_SP_SERIAL_CN > 0 && (q + 1) % QC_SL_SP_SERIAL_CN == 0)
-                        SP_TIE("+v"(msg[e]));  // next edge's chain starts after this output
+                    SP_TIE("+v"(msg[e]));  // next edge's chain starts after this output
                 });
         });
         // CV per block row through the LDS exchange
@@ -281,7 +238,7 @@ __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float*
                     }
                 });
             }
-            sl_barrier();
+            __syncthreads();
             float g[d];
             static_for<0, d>([&](auto tt) __attribute__((always_inline)) {
                 constexpr int t = decltype(tt)::value;
@@ -289,8 +246,8 @@ __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float*
                 if constexpr (s == 0) g[t] = msg[e0 + t];
                 else g[t] = Xv[nz_index<C>(r, t) * ROW + xb + s];
             });
-            cn_ds_row<d, QC_SL_SP_SERIAL_ROW, 0, DS_BLOCK, FIX>(g, cmax2, fixm);  // O(d) exclusive sets (common.h)
-            if constexpr (CMP) sl_barrier();  // every wave has read this row's v2c before the buffer takes its c2v
+            cn_ds_row<d, 1, 0, DS_BLOCK, FIX>(g, cmax2, fixm);  // O(d) exclusive sets (common.h)
+            if constexpr (CMP) __syncthreads();  // every wave has read this row's v2c before the buffer takes its c2v
             if (live) {
                 static_for<0, d>([&](auto tt) __attribute__((always_inline)) {
                     constexpr int t = decltype(tt)::value;
@@ -301,14 +258,14 @@ __device__ __forceinline__ void qc_sp_sl_unit(uint32_t unit_listed, const float*
                     }
                 });
             }
-            sl_barrier();
+            __syncthreads();
             static_for<0, d>([&](auto tt) __attribute__((always_inline)) {
                 constexpr int t = decltype(tt)::value;
                 constexpr int s = C::SHR[r][t];
                 if constexpr (s == 0) msg[e0 + t] = g[t];
                 else msg[e0 + t] = Xc[nz_index<C>(r, t) * ROW + xb + (Z - s)];
             });
-            if constexpr (CMP) sl_barrier();  // ... and its c2v before the next row's v2c lands in the buffer
+            if constexpr (CMP) __syncthreads();  // ... and its c2v before the next row's v2c lands in the buffer
         });
     }
     if (EARLY && (h ? done1 : done0)) {
@@ -354,20 +311,8 @@ void k_qc_sp_sl(const float* __restrict__ llr, int64_t B, int iters, float clamp
 // ds instruction's immediate.  LDS: 49 rotated circulants x 2 codewords x 81 x 4 B = 31.0 KiB per unit of
 // three waves, five units (15 waves) per CU, as the register-exchange kernel.  Arithmetic operation for
 // operation that kernel's (bitwise equal results; tests/test_gpu_parity.py).
-#ifndef QC_SL_SP_RS
-#define QC_SL_SP_RS 1
-#endif
 #ifndef QC_RS_WAVES_PER_SIMD
 #define QC_RS_WAVES_PER_SIMD 4
-#endif
-#ifndef QC_RS_SERIAL
-#define QC_RS_SERIAL 1  // the VN chains' ties (vn_excl_sums' TIE)
-#endif
-#ifndef QC_RS_SERIAL_ROW
-#define QC_RS_SERIAL_ROW 1  // the check rows' ties (cn_ds_row's SERIAL); 2: 59 VGPRs spilled
-#endif
-#ifndef QC_RS_ADDR_OPAQUE
-#define QC_RS_ADDR_OPAQUE 0  // 1: address VGPRs through an empty asm at each use (a v_mov each: 4.09 vs 4.28 M cw/s)
 #endif
 #ifndef QC_RS_DS_BLOCK
 // check rows (d = 20) in blocks of this many edges (common.h cn_ds_row; bitwise the same outputs).  20: one block,
@@ -376,30 +321,6 @@ void k_qc_sp_sl(const float* __restrict__ llr, int64_t B, int iters, float clamp
 // loop and read after it) go to scratch around the loop — no scratch access inside it (tests/test_kernel_resources.py);
 // recomputing the output indices after the loop moved a spill INTO the loop instead.
 #define QC_RS_DS_BLOCK 20
-#endif
-#ifndef QC_RS_PRIO
-// 1: s_setprio 1 over the latency-bound VN phase (short chains between LDS loads), 0 over the issue-bound CN phase,
-// so a SIMD issues the VN waves' loads as soon as they are ready and fills the gaps with CN work: 4.35 -> 4.67 M
-// cw/s (A/B profiles/r04/ab/ab_rs.txt); 2: the reverse, 4.25; 3: as 1, and the CN phase's row gathers at 1 too
-#define QC_RS_PRIO 1
-#endif
-#ifndef QC_RS_MASK_IDLE
-#define QC_RS_MASK_IDLE 0  // A/B -1.5 % (profiles/r04/ab/ab_mask.txt)
-#endif
-#ifndef QC_RS_IDLE_DUP
-#define QC_RS_IDLE_DUP 0  // 1: idle lanes l >= 27 shadow lane l - 27 (same loads, same values) and store too: no exec branches
-#endif
-#ifndef QC_RS_ROW_LAG
-#define QC_RS_ROW_LAG 0  // 1: the check rows' ties lag one edge (two edges' outputs in flight, common.h)
-#endif
-#ifndef QC_RS_VPF
-#define QC_RS_VPF 0  // 1: the VN phase loads column j + 1's messages before column j's chains and stores
-#endif
-#ifndef QC_RS_CPF
-#define QC_RS_CPF 0  // k > 0: the CN phase loads the last k edges of row r + 1 (read first) before row r's chains
-#endif
-#ifndef QC_RS_L
-#define QC_RS_L 0  // where L lives: 0 VGPRs (loaded once), 2 re-read from global memory at every use (3.64 vs 4.09)
 #endif
 
 template <class C>
@@ -426,12 +347,6 @@ template <class C>
 constexpr int rs_rot_total() {
     return rs_rot_index<C>(C::MB - 1, C::DEG[C::MB - 1] - 1) + (C::SHR[C::MB - 1][C::DEG[C::MB - 1] - 1] != 0);
 }
-template <class C>
-constexpr int rs_max_col_deg() {
-    int m = 1;
-    for (int j = 0; j < C::NB; ++j) m = col_deg<C>(j) > m ? col_deg<C>(j) : m;
-    return m;
-}
 template <int Z>
 constexpr int rs_q() {  // the smallest Q with Q * Q >= Z (9 for 81)
     int q = 1;
@@ -439,10 +354,6 @@ constexpr int rs_q() {  // the smallest Q with Q * Q >= Z (9 for 81)
     return q;
 }
 
-// QC_RS_DIAG_NOBAR (DIAGNOSTIC BUILDS ONLY, wrong results): the two barriers per iteration removed, to price them
-#ifndef QC_RS_DIAG_NOBAR
-#define QC_RS_DIAG_NOBAR 0
-#endif
 template <class C, int PASS>  // PASS, unit_listed: as qc_sp_sl_unit's
 __device__ __forceinline__ void qc_sp_rs_unit(uint32_t unit_listed, const float* __restrict__ llr, int64_t B, int iters,
                                               float clamp, int flags, uint8_t* __restrict__ bits,
@@ -465,12 +376,9 @@ __device__ __forceinline__ void qc_sp_rs_unit(uint32_t unit_listed, const float*
     const int64_t cw = unit * 2 + h;
     const bool live = l < ZL;                // lane carries a frame position (stores are live lanes only)
     const bool valid = live && cw < B;
-    // idle lanes read at their wave's first position (a broadcast, see k_qc_sp_sl) and never store; with
-    // QC_RS_IDLE_DUP they shadow lane l - ZL instead — the same loads, so the same values, written to the same
-    // slots by the same instruction — and the stores need no exec mask
-    auto pos_of = [&](int ll) { return QC_SL_POS_STRIDE ? S * ll + k : ll + ZL * k; };  // see QC_SL_POS_STRIDE
-    const int zc = live ? pos_of(l) : (QC_RS_IDLE_DUP ? pos_of(l - ZL) : pos_of(0));
-    const bool store = QC_RS_IDLE_DUP ? true : live;
+    // idle lanes read at their wave's first position (a broadcast, see k_qc_sp_sl) and never store
+    auto pos_of = [&](int ll) { return S * ll + k; };  // strided positions (above)
+    const int zc = live ? pos_of(l) : pos_of(0);
     // byte addresses of this lane's slot for a = 0 .. NA-1 (check side) and b = 0 .. Q-1 (variable side)
     int aC[NA], aV[Q];
 #pragma unroll
@@ -488,35 +396,24 @@ __device__ __forceinline__ void qc_sp_rs_unit(uint32_t unit_listed, const float*
     // slot of edge (r, t) seen from the check side / the variable side (compile-time rotation, runtime base)
     auto cref = [&](auto rr, auto tt) __attribute__((always_inline)) -> float& {
         constexpr int r = decltype(rr)::value, t = decltype(tt)::value, s = C::SHR[r][t];
-        int a = aC[s / Q];
-        if constexpr (QC_RS_ADDR_OPAQUE) asm volatile("" : "+v"(a));  // one address VGPR per value of a
+        const int a = aC[s / Q];
         return *reinterpret_cast<float*>(Xb + a + rs_rot_index<C>(r, t) * CROW);
     };
     auto vref = [&](auto rr, auto tt) __attribute__((always_inline)) -> float& {
         constexpr int r = decltype(rr)::value, t = decltype(tt)::value, s = C::SHR[r][t];
-        int a = aV[s % Q];
-        if constexpr (QC_RS_ADDR_OPAQUE) asm volatile("" : "+v"(a));
+        const int a = aV[s % Q];
         return *reinterpret_cast<float*>(Xb + a + rs_rot_index<C>(r, t) * CROW);
     };
-    // L = -llr (bp.py:47) of this lane's variable in block column j: in VGPRs, or re-read at every use (L2)
-    const bool lval = QC_RS_IDLE_DUP ? cw < B : valid;  // shadow lanes load their partner's L
-    const float* const lp = llr + (lval ? cw * N : 0);
-    float Lreg[QC_RS_L == 0 ? NB : 1];
-    auto Lload = [&](int j, bool opaque) __attribute__((always_inline)) {
-        int z = zc;
-        if (opaque) asm volatile("" : "+v"(z));
-        int t = z + C::PHI[j];
-        t -= (t >= Z) ? Z : 0;
-        return lval ? -lp[j * Z + t] : 0.0f;
-    };
-    if constexpr (QC_RS_L == 0) {
+    // L = -llr (bp.py:47) of this lane's variable in block column j, in VGPRs
+    const float* const lp = llr + (valid ? cw * N : 0);
+    float Lreg[NB];
 #pragma unroll
-        for (int j = 0; j < NB; ++j) Lreg[j] = Lload(j, false);
+    for (int j = 0; j < NB; ++j) {
+        int t = zc + C::PHI[j];
+        t -= (t >= Z) ? Z : 0;
+        Lreg[j] = valid ? -lp[j * Z + t] : 0.0f;
     }
-    auto Lr_at = [&](int j) __attribute__((always_inline)) {
-        if constexpr (QC_RS_L == 0) return Lreg[j];
-        else return Lload(j, true);
-    };
+    auto Lr_at = [&](int j) __attribute__((always_inline)) { return Lreg[j]; };
     float m0[N0 > 0 ? N0 : 1];  // messages of the rotation-0 circulants (both frames agree)
 #pragma unroll
     for (int e = 0; e < N0; ++e) m0[e] = 0.0f;
@@ -554,52 +451,30 @@ __device__ __forceinline__ void qc_sp_rs_unit(uint32_t unit_listed, const float*
         return sp_z(Lr_at(j), Ssum);
     };
 
-    // QC_RS_MASK_IDLE: idle lanes (l >= ZL) sit the iteration loop out, EXEC-masked (they never store; every wave
-    // keeps live lanes, so each still meets both barriers of every iteration)
-    const bool loop_lane = !QC_RS_MASK_IDLE || live;
     constexpr bool FIX = PASS == 2;
     // the rule applies per codeword (common.h): this lane's codeword's bit of the unit's flag
     uint32_t fixm = 0x7fffffffu;
     if constexpr (FIX) fixm = ((qc_sp_zflag(zlist, B)[unit] >> h) & 1u) ? 0x7fffffffu : 0u;
-    if (loop_lane)
     for (int it = 0; it < iters; ++it) {
         // VN phase (variable frame): every column's c2v -> v2c as signed a, written back in place
-        if constexpr (QC_RS_PRIO == 1 || QC_RS_PRIO == 3) __builtin_amdgcn_s_setprio(1);
-        if constexpr (QC_RS_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-        if constexpr (QC_RS_PRIO == 4) __builtin_amdgcn_s_setprio(3);
-        constexpr int DV = rs_max_col_deg<C>();
-        float xn[DV];  // QC_RS_VPF: the next column's messages, loaded one column ahead
-        if constexpr (QC_RS_VPF) {
-            static_for<0, col_deg<C>(0)>([&](auto kk) __attribute__((always_inline)) {
-                xn[kk] = vload(std::integral_constant<int, 0>{}, kk);
-            });
-        }
+        __builtin_amdgcn_s_setprio(1);
         static_for<0, NB>([&](auto jj) __attribute__((always_inline)) {
             constexpr int j = decltype(jj)::value;
             constexpr int dj = col_deg<C>(j);
             float x[dj];
-            static_for<0, dj>([&](auto kk) __attribute__((always_inline)) {
-                if constexpr (QC_RS_VPF) x[kk] = xn[kk];
-                else x[kk] = vload(jj, kk);
-            });
-            if constexpr (QC_RS_VPF && j + 1 < NB) {  // other slots than column j's: no hazard with its stores
-                static_for<0, col_deg<C>(j + 1)>([&](auto kk) __attribute__((always_inline)) {
-                    xn[kk] = vload(std::integral_constant<int, j + 1>{}, kk);
-                });
-            }
+            static_for<0, dj>([&](auto kk) __attribute__((always_inline)) { x[kk] = vload(jj, kk); });
             const float Lj = Lr_at(j);
-            vn_excl_sums<dj, QC_RS_SERIAL>(
+            vn_excl_sums<dj, 1>(
                 [&](auto kk) __attribute__((always_inline)) { return x[kk]; },
                 [&](auto kk, float Ssum) __attribute__((always_inline)) {
                     x[kk] = vn_signed_a(sp_vn_arg(Lj, Ssum));  // the (D, S) form's VC output (common.h)
-                    if constexpr (QC_RS_SERIAL > 0 && (decltype(kk)::value + 1) % QC_RS_SERIAL == 0)
-                        SP_TIE("+v"(x[kk]));
+                    SP_TIE("+v"(x[kk]));
                 });
             static_for<0, dj>([&](auto kk) __attribute__((always_inline)) {
                 constexpr int rt = col_rt(j, decltype(kk)::value), r = rt / 64, t = rt % 64;
                 if constexpr (C::SHR[r][t] == 0) m0[rs_zero_index<C>(r, t)] = x[kk];
             });
-            if (store) {
+            if (live) {
                 static_for<0, dj>([&](auto kk) __attribute__((always_inline)) {
                     constexpr int rt = col_rt(j, decltype(kk)::value), r = rt / 64, t = rt % 64;
                     if constexpr (C::SHR[r][t] != 0)
@@ -607,45 +482,30 @@ __device__ __forceinline__ void qc_sp_rs_unit(uint32_t unit_listed, const float*
                 });
             }
         });
-        if constexpr (!QC_RS_DIAG_NOBAR) __syncthreads();  // (QC_RS_DIAG_NOBAR: diagnostic builds only)
+        __syncthreads();
         // CN phase (check frame): every row's v2c -> c2v, written back in place
-        if constexpr (QC_RS_PRIO == 1 || QC_RS_PRIO == 3 || QC_RS_PRIO == 4) __builtin_amdgcn_s_setprio(0);
-        if constexpr (QC_RS_PRIO == 2) __builtin_amdgcn_s_setprio(1);
-        constexpr int KP = QC_RS_CPF > 0 ? QC_RS_CPF : 1;
-        float gn[KP];  // QC_RS_CPF: the last KP edges of the next row, loaded one row ahead
-        auto cpf = [&](auto rr) __attribute__((always_inline)) {
-            constexpr int r = decltype(rr)::value, d = C::DEG[r];
-            static_for<0, (KP < d ? KP : d)>([&](auto uu) __attribute__((always_inline)) {
-                constexpr int t = d - 1 - decltype(uu)::value;
-                if constexpr (C::SHR[r][t] != 0) gn[decltype(uu)::value] = cref(rr, std::integral_constant<int, t>{});
-            });
-        };
-        if constexpr (QC_RS_CPF > 0) cpf(std::integral_constant<int, 0>{});
+        __builtin_amdgcn_s_setprio(0);
         static_for<0, MB>([&](auto rr) __attribute__((always_inline)) {
             constexpr int r = decltype(rr)::value;
             constexpr int d = C::DEG[r];
-            if constexpr (QC_RS_PRIO == 3) __builtin_amdgcn_s_setprio(1);
             float g[d];
             static_for<0, d>([&](auto tt) __attribute__((always_inline)) {
                 constexpr int t = decltype(tt)::value;
                 if constexpr (C::SHR[r][t] == 0) g[t] = m0[rs_zero_index<C>(r, t)];
-                else if constexpr (QC_RS_CPF > 0 && t >= d - KP) g[t] = gn[d - 1 - t];
                 else g[t] = cref(rr, tt);
             });
-            if constexpr (QC_RS_PRIO == 3) __builtin_amdgcn_s_setprio(0);
-            if constexpr (QC_RS_CPF > 0 && r + 1 < MB) cpf(std::integral_constant<int, r + 1>{});
-            cn_ds_row<d, QC_RS_SERIAL_ROW, QC_RS_ROW_LAG, QC_RS_DS_BLOCK, FIX>(g, cmax2, fixm);  // O(d) exclusive sets (common.h)
+            cn_ds_row<d, 1, 0, QC_RS_DS_BLOCK, FIX>(g, cmax2, fixm);  // O(d) exclusive sets (common.h)
             static_for<0, d>([&](auto tt) __attribute__((always_inline)) {
                 constexpr int t = decltype(tt)::value;
                 if constexpr (C::SHR[r][t] == 0) m0[rs_zero_index<C>(r, t)] = g[t];
             });
-            if (store) {
+            if (live) {
                 static_for<0, d>([&](auto tt) __attribute__((always_inline)) {
                     if constexpr (C::SHR[r][decltype(tt)::value] != 0) cref(rr, tt) = g[decltype(tt)::value];
                 });
             }
         });
-        if constexpr (!QC_RS_DIAG_NOBAR) __syncthreads();  // (QC_RS_DIAG_NOBAR: diagnostic builds only)
+        __syncthreads();
     }
     // the output's lane coordinates recomputed after the loop — the lane id by v_mbcnt (the work-item id VGPR of
     // the launch is long gone), the slot wave k is scalar — instead of kept across it: the values set before the

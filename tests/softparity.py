@@ -37,7 +37,7 @@ import numpy as np
 
 TOL = 1e-5
 # (kind, golden set, implementation) -> (entries where the reference's fp32 is within 1e-5 and ours is not, the
-# maximum error on decoding failures): measured with the fma join (common.h DS_JOIN_FMA; GPU: the -m gpu suite
+# maximum error on decoding failures): measured with the fma join (common.h ds_join_out; GPU: the -m gpu suite
 # under LDPC_PARITY_MEASURE=1, every kernel family, profiles/r04/failure_bounds/; oracle: the CPU suite), collected
 # by scripts/failure_bounds.py, the maxima rounded up in the third digit.  Unlisted sets: count 0.
 FAILURE_BOUNDS = {

@@ -60,7 +60,7 @@ def test_interleaved_streams_equal_serial(monkeypatch):
 
 
 def test_more_caller_streams_than_auxiliary_sets(monkeypatch):
-    """The library keeps at most 16 auxiliary-stream sets per host thread, one per caller stream (csrc/qc.hip
+    """The library keeps at most 16 auxiliary-stream sets per host thread, one per caller stream (csrc/aux_streams.hip
     aux_get); a 17th caller stream evicts the least recently used set while earlier decodes may still run on it.
     Decodes forked from 20 caller streams, twice round, still equal the serial decodes."""
     monkeypatch.setenv("LDPC_IRA_BUDGET_MB", "2")

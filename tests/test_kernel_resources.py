@@ -9,7 +9,7 @@ waves / units whose LLRs hold an exact zero (erasures, quantized LLRs), which ma
 
     [1] (648,1/2) min-sum 50 it          k_qc_ms_ph<Wifi648_12, false, false, 0>
     [2] (1944,5/6) tanh-SP, 16-QAM OFDM   k_qc_sp_rs<Wifi1944_56, 1> (fixed count), k_qc_sp_sl<Wifi1944_56, *, 1>
-                                          (early stop; the fixed-count sliced kernel remains for QC_SL_SP_RS=0)
+                                          (early stop only: fixed count runs the resident kernel)
     [3] (1296,2/3) 5-bit min-sum 20 it ES k_qc_qms_pk<Wifi1296_23, *, *>  (packed fp16, two codewords per lane)
     [4] DVB-S2 64800 rate 1/2, 50 it      IRA kernels (ira.hip: k_ira_vn<8, *>, k_ira_cn<8, true, *>, k_ira_load,
                                           k_ira_out); the generic CSR kernels at degree bound 8 (k_vn_ms/k_cn_ms,
