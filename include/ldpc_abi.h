@@ -64,10 +64,33 @@ enum {
  * so the result is defined bit for bit; ties in idx cannot change a value (then min2 == min1).  ZTHR is the
  * hard-decision threshold of every fp32 decoder here (-1.7881392e-07f).  Implemented for the compiled 802.11n
  * codes with Z <= 64, LDPC_ALGO_MIN_SUM, fp32, through ldpc_decode_ex / ldpc_decode (host or device
- * pointers); every other combination (tanh-SP, quantized min-sum, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph
- * without a compiled QC code, IRA graphs, Z = 81, ldpc_decode_weighted, ldpc_decode_x0,
- * ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says which.  The flag is additive: ldpc_params and
- * LDPC_ABI_VERSION are unchanged, and nothing changes while it is clear.  Needs no kernel workspace. */
+ * pointers).
+ *
+ * LDPC_F_LAYERED with LDPC_ALGO_QMIN_SUM — layered quantized min-sum, integers throughout, per codeword (the
+ * quantizer, sign convention and decision rule of the flooding LDPC_ALGO_QMIN_SUM):
+ *
+ *   q_v = sat(rint(llr_v * (1.0f / qstep)), qmax) in fp32;  L_v = -q_v
+ *   APP_v = L_v;  c2v[e] = 0 for every edge
+ *   for it in 0 .. iters-1:
+ *     for check c in ascending order:                                        (row-serial)
+ *       for each edge e of c:  t_e = APP_v(e) - c2v[e]                        (exact, |t_e| <= app_max + qmax)
+ *                              a_e = max(min(|t_e|, qmax) - beta, 0)          (magnitudes capped at qmax)
+ *       min1 <= min2 = the two smallest a_e, idx = an edge attaining min1, sgn = xor over e of (t_e < 0)
+ *       c2v[e] = (sgn ^ (t_e < 0)) ? -m : m,   m = (e == idx) ? min2 : min1
+ *       APP_v(e) = sat(t_e + c2v[e], app_max)
+ *     LDPC_F_EARLY_STOP: after the full sweep, stop the codeword when H * (APP < 0) = 0
+ *   z_v = 0.5f * APP_v;  bit_v = (APP_v < 0);  iters_used = sweeps run
+ *
+ * t_e is not saturated to qmax (that would cap every posterior at 2 qmax): only the magnitude entering the minima
+ * is.  Zero has no sign: a zero t_e makes every other output of its check zero and its own output does not depend
+ * on its own sign, so an implementation may carry -0 and z is defined by value, not by bit pattern.  Ties in idx
+ * cannot change a value.  Implemented for the compiled codes with 32 < Z <= 64 ((1296,2/3)) in packed fp16, exact
+ * while app_max + 2*qmax <= 2047; a larger bound, or another lifting size, returns LDPC_EUNSUPPORTED.
+ *
+ * Every other combination (tanh-SP, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph without a compiled QC code, IRA
+ * graphs, Z = 81, ldpc_decode_weighted, ldpc_decode_x0, ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says
+ * which.  The flag is additive: ldpc_params and LDPC_ABI_VERSION are unchanged, and nothing changes while it is
+ * clear.  Needs no kernel workspace. */
 
 typedef struct {
     int32_t iters;   /* iterations (maximum when LDPC_F_EARLY_STOP)                         */

@@ -190,8 +190,11 @@ static int layered_check(const ldpc_graph* g, const ldpc_params* p) {
     if (p->flags & LDPC_F_FORCE_GENERIC) why = "LDPC_F_FORCE_GENERIC: the generic CSR kernels run the flooding schedule only";
     else if (!g->qc) why = g->ira ? "an IRA (DVB-S2) graph: layered decoding needs a compiled 802.11n QC code"
                                   : "a graph without a compiled QC code: layered decoding needs 802.11n (648,1/2) or (1296,2/3)";
-    else if (p->algo == LDPC_ALGO_TANH_SP) why = "tanh sum-product: layered decoding is float min-sum only";
-    else if (p->algo == LDPC_ALGO_QMIN_SUM) why = "quantized min-sum: layered decoding is float min-sum only";
+    else if (p->algo == LDPC_ALGO_TANH_SP) why = "tanh sum-product: layered decoding is min-sum only";
+    else if (p->algo == LDPC_ALGO_QMIN_SUM && !qc_lay_pk_serves_z(qc_z(g->qc)))
+        why = "quantized min-sum at this lifting size: the packed layered kernel serves 32 < Z <= 64";
+    else if (p->algo == LDPC_ALGO_QMIN_SUM && !(p->flags & LDPC_F_F64) && !qc_lay_pk_exact(*p))
+        why = "these quantizer limits: the packed fp16 layered kernel is exact while app_max + 2*qmax <= 2047";
     else if (p->flags & LDPC_F_F64) why = "LDPC_F_F64: layered decoding is fp32 only";
     return set_error(LDPC_EUNSUPPORTED, "LDPC_F_LAYERED is not implemented for %s", why);
 }

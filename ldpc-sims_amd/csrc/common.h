@@ -454,8 +454,11 @@ size_t qc_workspace(const QCSpec* s, int64_t B, const ldpc_params& p);
 int qc_decode(const QCSpec* s, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
               int32_t* iters_used, char* ws, hipStream_t st);
 
-// Layered (row-serial) min-sum for the compiled QC codes with Z <= 64 (qc_lay.hip, LDPC_F_LAYERED): float
-// min-sum only, no workspace, asynchronous on st.
+// Layered (row-serial) min-sum for the compiled QC codes with Z <= 64 (LDPC_F_LAYERED): float min-sum (qc_lay.hip),
+// and quantized min-sum at 32 < Z <= 64 while app_max + 2 qmax <= 2047 (qc_lay_pk.hip, packed fp16); no workspace,
+// asynchronous on st.
+bool qc_lay_pk_serves_z(int z);
+bool qc_lay_pk_exact(const ldpc_params& p);
 bool qc_lay_supports(const QCSpec* s, const ldpc_params& p);
 int qc_lay_decode(const QCSpec* s, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
                   int32_t* iters_used, hipStream_t st);

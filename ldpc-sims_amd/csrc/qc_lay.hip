@@ -22,7 +22,7 @@
 //   * LDS carries nothing but the rotation transport: one 64-lane row per wave written with
 //     ds_write_addtid_b32 (fixed count, Z <= 32), ds_bpermute otherwise — the choice the flooding kernels
 //     measured per code.
-#include "qc_common.h"
+#include "qc_lay_frames.h"
 
 #include <cstdint>
 
@@ -40,36 +40,6 @@ namespace ldpc {
 #endif
 template <bool EARLY>
 constexpr int lay_tpb() { return EARLY ? QC_LAY_TPB_EARLY : 256; }
-
-// The floating frame of every block column, tabulated once per code: end[j] = the shift of the last base
-// row touching column j (the frame L_j is loaded in, every sweep ends in and the outputs are stored from);
-// rho[r][t] = the rotation that brings slot t's column from the frame of the row that touched it before
-// (cyclically) into row r's.
-template <class C>
-struct LayFrames {
-    struct Tab {
-        int rho[C::MB][C::MAXDC], end[C::NB];
-    };
-    static constexpr Tab make() {
-        Tab f{};
-        for (int j = 0; j < C::NB; ++j) {
-            int last = 0;
-            for (int r = 0; r < C::MB; ++r)
-                for (int t = 0; t < C::DEG[r]; ++t)
-                    if (C::COL[r][t] == j) last = C::SH[r][t];
-            f.end[j] = last;
-            int prev = last;
-            for (int r = 0; r < C::MB; ++r)
-                for (int t = 0; t < C::DEG[r]; ++t)
-                    if (C::COL[r][t] == j) {
-                        f.rho[r][t] = (C::SH[r][t] - prev + C::Z) % C::Z;
-                        prev = C::SH[r][t];
-                    }
-        }
-        return f;
-    }
-    static constexpr Tab T = make();
-};
 
 template <class C, bool EARLY, int NORM>
 __global__ __launch_bounds__(256, EARLY ? QC_LAY_WAVES_PER_SIMD_EARLY : QC_LAY_WAVES_PER_SIMD) void k_qc_ms_lay(
@@ -304,14 +274,23 @@ static LayLaunch lay_launcher(const QCSpec* s) {
     }
 }
 
+// packed fp16 layered quantized min-sum (qc_lay_pk.hip): the compiled codes with 32 < Z <= 64
+bool qc_lay_pk_serves_z(int z);
+bool qc_lay_pk_exact(const ldpc_params& p);
+int qc_launch_qms_lay_wifi1296_23(const void* llr, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
+                                  int32_t* used, hipStream_t st);
+
 bool qc_lay_supports(const QCSpec* s, const ldpc_params& p) {
-    return s && lay_launcher(s) && p.algo == LDPC_ALGO_MIN_SUM && !(p.flags & LDPC_F_F64);
+    if (!s || !lay_launcher(s) || (p.flags & LDPC_F_F64)) return false;
+    if (p.algo == LDPC_ALGO_QMIN_SUM) return qc_lay_pk_serves_z(qc_z(s)) && qc_lay_pk_exact(p);
+    return p.algo == LDPC_ALGO_MIN_SUM;
 }
 
 int qc_lay_decode(const QCSpec* s, const void* llr, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
                   int32_t* iters_used, hipStream_t st) {
     if (!qc_lay_supports(s, p)) return set_error(LDPC_EUNSUPPORTED, "no layered kernel for this code / algorithm");
     if (B <= 0) return LDPC_OK;
+    if (p.algo == LDPC_ALGO_QMIN_SUM) return qc_launch_qms_lay_wifi1296_23(llr, B, p, bits, soft, iters_used, st);
     return lay_launcher(s)(llr, B, p, bits, soft, iters_used, st);
 }
 

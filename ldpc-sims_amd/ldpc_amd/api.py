@@ -165,7 +165,8 @@ class Decoder:
         torch GPU tensors only (tanh-SP, no early stop, generic kernels).
         ``schedule``: "flooding" (default) or "layered" — row-serial min-sum (``LDPC_F_LAYERED`` in
         ``include/ldpc_abi.h``): float min-sum on the 802.11n codes with Z <= 64, about half the iterations of
-        flooding for the same error rate; anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
+        flooding for the same error rate, and quantized min-sum (``algo="qms"``) on (1296,2/3) while
+        ``app_max + 2*qmax <= 2047``; anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
         is_torch = type(llr).__module__.startswith("torch")
         on_gpu = is_torch and llr.is_cuda
         fdt = np.float64 if precision == "f64" else np.float32

@@ -290,7 +290,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--early-stop", action="store_true")
     ap.add_argument("--schedule", default="flooding", choices=["flooding", "layered"],
-                    help="layered: row-serial min-sum (802.11n codes with Z <= 64, --algo minsum)")
+                    help="layered: row-serial min-sum (802.11n codes with Z <= 64: --algo minsum; (1296,2/3): --algo qms too)")
     ap.add_argument("--encoder", default="auto", choices=["auto", "torch"],
                     help="auto: the library's HIP encoder where the code has one; torch: synth.DeviceEncoder")
     ap.add_argument("--mod", default="bpsk", choices=["bpsk", "qpsk-ofdm", "16qam-ofdm"])

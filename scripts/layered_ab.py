@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """A/B of the layered against the flooding schedule on bench.py's config [1] workload — (648,1/2) min-sum,
-B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — in one process on one GPU:
+B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — or, with --algo qms, on config [3]'s:
+(1296,2/3), 5-bit LLRs (qmax 15, app_max 127, --qstep), early stop (--early-stop), flooding-20 against layered-10;
+--fixed-pair adds the same pair without early stop under "fixed_count".  In one process on one GPU:
 
   * block error rate of both legs at every Eb/N0 point (ldpc_count_errors), flooding at --flood-iters (50)
     and layered at --lay-iters (25);
@@ -9,6 +11,8 @@ B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — in one pr
     two times and their ratio, so the pair-to-pair spread stands next to the difference it qualifies.
 
     python scripts/layered_ab.py --out profiles/layered_ab.json [--pairs 12] [--launches 11]
+    python scripts/layered_ab.py --algo qms --code wifi1296_23 --flood-iters 20 --lay-iters 10 --early-stop \
+        --fixed-pair --out profiles/layered/ab_q5.json
 
 Needs a GPU; writes one JSON record.
 """
@@ -31,6 +35,10 @@ def main():
     ap.add_argument("--ebn0", default="0:0.5:5")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--clamp", type=float, default=20.0)
+    ap.add_argument("--algo", default="minsum", choices=["minsum", "qms"])
+    ap.add_argument("--qstep", type=float, default=1.0, help="qms: LLR quantizer step (qmax 15, app_max 127)")
+    ap.add_argument("--early-stop", action="store_true")
+    ap.add_argument("--fixed-pair", action="store_true", help="with --early-stop: time the fixed-count pair too")
     ap.add_argument("--flood-iters", type=int, default=50)
     ap.add_argument("--lay-iters", type=int, default=25)
     ap.add_argument("--pairs", type=int, default=12)
@@ -66,56 +74,63 @@ def main():
         llrs.append(x)
     bits = torch.empty((B, n), dtype=torch.uint8, device="cuda")
 
-    legs = {}
-    for name, iters, sched in (("flooding", a.flood_iters, "flooding"), ("layered", a.lay_iters, "layered")):
-        p = dec.params(iters, "minsum", a.clamp, device_ptrs=True, schedule=sched)
-        wsb = dec.workspace_bytes(B, p)
-        legs[name] = dict(p=p, wsb=wsb, ws=torch.empty((max(wsb, 1),), dtype=torch.uint8, device="cuda"),
-                          iters=iters, kernel_path=dec.kernel_path(p))
+    def measure(a, early_stop):
+        legs = {}
+        for name, iters, sched in (("flooding", a.flood_iters, "flooding"), ("layered", a.lay_iters, "layered")):
+            p = dec.params(iters, a.algo, a.clamp, early_stop=early_stop, qstep=a.qstep, device_ptrs=True, schedule=sched)
+            wsb = dec.workspace_bytes(B, p)
+            legs[name] = dict(p=p, wsb=wsb, ws=torch.empty((max(wsb, 1),), dtype=torch.uint8, device="cuda"),
+                              iters=iters, kernel_path=dec.kernel_path(p))
 
-    def launch(leg, x):
-        _abi.check(lib.ldpc_decode_ex(dec._h, x.data_ptr(), B, leg["p"], bits.data_ptr(), None, None,
-                                      leg["ws"].data_ptr(), leg["wsb"], st))
+        def launch(leg, x):
+            _abi.check(lib.ldpc_decode_ex(dec._h, x.data_ptr(), B, leg["p"], bits.data_ptr(), None, None,
+                                          leg["ws"].data_ptr(), leg["wsb"], st))
 
-    bler = {}
-    for name, leg in legs.items():
-        counts = torch.zeros((len(ebn0), 3), dtype=torch.int64, device="cuda")
-        for i, x in enumerate(llrs):
-            launch(leg, x)
-            _abi.check(lib.ldpc_count_errors(bits.data_ptr(), cw.data_ptr(), B, n, k, counts[i].data_ptr(), st))
-        c = counts.cpu().numpy().astype(np.float64)
-        bler[name] = dict(coded_bler=(c[:, 1] / c[:, 2]).tolist(), coded_ber_info=(c[:, 0] / (c[:, 2] * k)).tolist())
+        bler = {}
+        for name, leg in legs.items():
+            counts = torch.zeros((len(ebn0), 3), dtype=torch.int64, device="cuda")
+            for i, x in enumerate(llrs):
+                launch(leg, x)
+                _abi.check(lib.ldpc_count_errors(bits.data_ptr(), cw.data_ptr(), B, n, k, counts[i].data_ptr(), st))
+            c = counts.cpu().numpy().astype(np.float64)
+            bler[name] = dict(coded_bler=(c[:, 1] / c[:, 2]).tolist(), coded_ber_info=(c[:, 0] / (c[:, 2] * k)).tolist())
 
-    def timed(leg):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for s in range(a.launches):
-            launch(leg, llrs[s % len(llrs)])
-        e1.record(stream)
-        return e0, e1
+        def timed(leg):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for s in range(a.launches):
+                launch(leg, llrs[s % len(llrs)])
+            e1.record(stream)
+            return e0, e1
 
-    for w in range(a.warmup):
-        launch(legs["flooding" if w % 2 == 0 else "layered"], llrs[w % len(llrs)])
-    sampler = ClockSampler(0)
-    with sampler:
-        events = [(timed(legs["flooding"]), timed(legs["layered"])) for _ in range(a.pairs)]  # no gap between legs
-        torch.cuda.synchronize()
-    pairs = []
-    for (f0, f1), (l0, l1) in events:
-        f, l = f0.elapsed_time(f1) / a.launches, l0.elapsed_time(l1) / a.launches
-        pairs.append(dict(flooding_ms=f, layered_ms=l, layered_over_flooding_cw_per_s=f / l))
-    ratios = [q["layered_over_flooding_cw_per_s"] for q in pairs]
-    out = dict(code=a.code, batch=B, ebn0_db=ebn0.tolist(), seed=a.seed, clamp=a.clamp, launches_per_leg=a.launches,
-               library=_abi.library_digest(), device=torch.cuda.get_device_name(0),
-               legs={nm: dict(iters=lg["iters"], kernel_path=lg["kernel_path"], **bler[nm]) for nm, lg in legs.items()},
-               pairs=pairs, clock=sampler.summary())
-    for nm, key in (("flooding", "flooding_ms"), ("layered", "layered_ms")):
-        ms = [q[key] for q in pairs]
-        out["legs"][nm].update(launch_ms_median=statistics.median(ms), launch_ms_min=min(ms), launch_ms_max=max(ms),
-                               ms_per_sweep=statistics.median(ms) / legs[nm]["iters"],
-                               cw_per_s=B / (statistics.median(ms) * 1e-3))
-    out["ratio_median"] = statistics.median(ratios)
-    out["ratio_min"], out["ratio_max"] = min(ratios), max(ratios)
+        for w in range(a.warmup):
+            launch(legs["flooding" if w % 2 == 0 else "layered"], llrs[w % len(llrs)])
+        sampler = ClockSampler(0)
+        with sampler:
+            events = [(timed(legs["flooding"]), timed(legs["layered"])) for _ in range(a.pairs)]  # no gap between legs
+            torch.cuda.synchronize()
+        pairs = []
+        for (f0, f1), (l0, l1) in events:
+            f, l = f0.elapsed_time(f1) / a.launches, l0.elapsed_time(l1) / a.launches
+            pairs.append(dict(flooding_ms=f, layered_ms=l, layered_over_flooding_cw_per_s=f / l))
+        ratios = [q["layered_over_flooding_cw_per_s"] for q in pairs]
+        out = dict(code=a.code, algo=a.algo, early_stop=early_stop, qstep=a.qstep, batch=B, ebn0_db=ebn0.tolist(), seed=a.seed, clamp=a.clamp, launches_per_leg=a.launches,
+                   library=_abi.library_digest(), device=torch.cuda.get_device_name(0),
+                   legs={nm: dict(iters=lg["iters"], kernel_path=lg["kernel_path"], **bler[nm]) for nm, lg in legs.items()},
+                   pairs=pairs, clock=sampler.summary())
+        for nm, key in (("flooding", "flooding_ms"), ("layered", "layered_ms")):
+            ms = [q[key] for q in pairs]
+            out["legs"][nm].update(launch_ms_median=statistics.median(ms), launch_ms_min=min(ms), launch_ms_max=max(ms),
+                                   ms_per_sweep=statistics.median(ms) / legs[nm]["iters"],
+                                   cw_per_s=B / (statistics.median(ms) * 1e-3))
+        out["ratio_median"] = statistics.median(ratios)
+        out["ratio_min"], out["ratio_max"] = min(ratios), max(ratios)
+        return out, legs
+
+    out, legs = measure(a, a.early_stop)
+    if a.early_stop and a.fixed_pair:
+        out["fixed_count"] = measure(a, False)[0]
+        print("fixed count:", json.dumps({kk: out["fixed_count"][kk] for kk in ("ratio_median", "ratio_min", "ratio_max")}))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
