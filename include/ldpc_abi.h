@@ -66,6 +66,28 @@ enum {
  * codes with Z <= 64, LDPC_ALGO_MIN_SUM, fp32, through ldpc_decode_ex / ldpc_decode (host or device
  * pointers).
  *
+ * LDPC_F_LAYERED on an IRA (DVB-S2-structured) graph — the same conventions, but a layer is one ROW of checks: with
+ * m = 360 q checks, check c = a + q b is (row a, position b), and the 360 checks of a row are parallel:
+ *
+ *   APP_v = L_v + (+0.0f), L = -llr;  c2v[e] = +0.0f
+ *   for it in 0 .. iters-1:
+ *     for a in 0 .. q-1:                                        (layer = checks {c : c mod q == a})
+ *       every check c of the layer, from the posteriors as they stood BEFORE the layer:
+ *         t_e = APP_v(e) - c2v[e];  min1, min2, sgn over the check's t_e;  new_e exactly as the text above
+ *       every variable v with ONE edge e in the layer:   APP_v = t_e + new_e
+ *       every variable v with TWO edges e1, e2 there:    APP_v = APP_v + ((new_e1 - c2v[e1]) + (new_e2 - c2v[e2]))
+ *       c2v[e] = new_e
+ *     LDPC_F_EARLY_STOP: after the full sweep, stop the codeword when H * (APP <= 2*ZTHR) = 0
+ *   z_v = 0.5f * APP_v;  bit_v = z_v <= ZTHR;  iters_used = sweeps run
+ *
+ * Every value is one correctly rounded fp32 operation; the two-edge sum is commutative, and the minima and the sign
+ * do not depend on the order of a check's edges.  The staircase edges of a layer never share a variable (q >= 2); an
+ * information variable has two edges in a layer when its group of 360 meets that row twice (8 of the 90 rows of
+ * DVB-S2 rate 1/2).  Implemented for LDPC_ALGO_MIN_SUM, fp32, on any graph with the IRA structure whose n - m
+ * information posteriors fit the 160 KiB of LDS of a workgroup and in which no group meets a row three or more
+ * times; otherwise LDPC_EUNSUPPORTED, naming the reason.  Needs a kernel workspace (ldpc_workspace_size): 16 m
+ * bytes per resident workgroup, not per codeword.
+ *
  * LDPC_F_LAYERED with LDPC_ALGO_QMIN_SUM — layered quantized min-sum, integers throughout, per codeword (the
  * quantizer, sign convention and decision rule of the flooding LDPC_ALGO_QMIN_SUM):
  *
@@ -87,10 +109,10 @@ enum {
  * cannot change a value.  Implemented for the compiled codes with 32 < Z <= 64 ((1296,2/3)) in packed fp16, exact
  * while app_max + 2*qmax <= 2047; a larger bound, or another lifting size, returns LDPC_EUNSUPPORTED.
  *
- * Every other combination (tanh-SP, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph without a compiled QC code, IRA
- * graphs, Z = 81, ldpc_decode_weighted, ldpc_decode_x0, ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says
- * which.  The flag is additive: ldpc_params and LDPC_ABI_VERSION are unchanged, and nothing changes while it is
- * clear.  Needs no kernel workspace. */
+ * Every other combination (tanh-SP, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph with neither a compiled QC code nor
+ * the IRA structure, quantized min-sum on IRA graphs, Z = 81, ldpc_decode_weighted, ldpc_decode_x0,
+ * ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says which.  The flag is additive: ldpc_params and LDPC_ABI_VERSION are unchanged, and nothing changes while it is
+ * clear.  The 802.11n forms need no kernel workspace. */
 
 typedef struct {
     int32_t iters;   /* iterations (maximum when LDPC_F_EARLY_STOP)                         */
@@ -127,7 +149,7 @@ int ldpc_graph_info(const ldpc_graph* g, int32_t* m, int32_t* n, int32_t* nnz, i
 
 /* The kernel family a decode with these params runs on this graph: "qc-z<Z>" (register-resident
  * quasi-cyclic kernels, 802.11n), "qc-z<Z>-layered" (the same codes with LDPC_F_LAYERED), "ira-z360" (DVB-S2-structured IRA codes, min-sum, fixed count or early
- * stop) or
+ * stop), "ira-z360-layered" (the same graphs with LDPC_F_LAYERED) or
  * "generic-csr" (any H).  Introspection only (benchmarks label their records with it); NULL on bad
  * arguments.  The string is thread-local and valid until the next call on this thread.  No reference
  * counterpart: the reference has one code path (dense masks, bp/masking.py). */

@@ -183,13 +183,22 @@ static bool use_qc(const ldpc_graph* g, const ldpc_params* p) {
 static bool use_lay(const ldpc_graph* g, const ldpc_params* p) {
     return (p->flags & LDPC_F_LAYERED) && g->qc && !(p->flags & LDPC_F_FORCE_GENERIC) && qc_lay_supports(g->qc, *p);
 }
+// the same on an IRA graph: the layered IRA kernel (ira_lay.hip) or nothing
+static bool use_ira_lay(const ldpc_graph* g, const ldpc_params* p) {
+    return (p->flags & LDPC_F_LAYERED) && g->ira && !(p->flags & LDPC_F_FORCE_GENERIC) && ira_lay_supports(g->ira, *p);
+}
 // LDPC_OK unless p asks for the layered schedule where it does not exist; the message names what is missing
 static int layered_check(const ldpc_graph* g, const ldpc_params* p) {
-    if (!(p->flags & LDPC_F_LAYERED) || use_lay(g, p)) return LDPC_OK;
+    if (!(p->flags & LDPC_F_LAYERED) || use_lay(g, p) || use_ira_lay(g, p)) return LDPC_OK;
     const char* why = "the code's lifting size: the layered kernel serves Z <= 64";
     if (p->flags & LDPC_F_FORCE_GENERIC) why = "LDPC_F_FORCE_GENERIC: the generic CSR kernels run the flooding schedule only";
-    else if (!g->qc) why = g->ira ? "an IRA (DVB-S2) graph: layered decoding needs a compiled 802.11n QC code"
-                                  : "a graph without a compiled QC code: layered decoding needs 802.11n (648,1/2) or (1296,2/3)";
+    else if (!g->qc && !g->ira)
+        why = "a graph without a compiled QC code or the IRA (DVB-S2) structure: layered decoding needs 802.11n "
+              "(648,1/2) or (1296,2/3), or an IRA graph";
+    else if (g->ira && p->algo == LDPC_ALGO_QMIN_SUM)
+        why = "quantized min-sum on an IRA (DVB-S2) graph: the layered IRA kernel is float min-sum only";
+    else if (g->ira && p->algo == LDPC_ALGO_MIN_SUM && !(p->flags & LDPC_F_F64) && ira_lay_why(g->ira))
+        why = ira_lay_why(g->ira);
     else if (p->algo == LDPC_ALGO_TANH_SP) why = "tanh sum-product: layered decoding is min-sum only";
     else if (p->algo == LDPC_ALGO_QMIN_SUM && !qc_lay_pk_serves_z(qc_z(g->qc)))
         why = "quantized min-sum at this lifting size: the packed layered kernel serves 32 < Z <= 64";
@@ -208,6 +217,7 @@ static size_t elem_size(const ldpc_params* p) { return (p->flags & LDPC_F_F64) ?
 // Workspace = kernel scratch followed (host-pointer callers only) by staging for llr/bits/soft/used.
 static size_t kernel_ws(const ldpc_graph* g, int64_t B, const ldpc_params* p) {
     if (use_lay(g, p)) return 0;
+    if (use_ira_lay(g, p)) return align256(ira_lay_workspace(g->ira, B, *p));
     if (use_qc(g, p)) return align256(qc_workspace(g->qc, B, *p));
     if (use_ira(g, p)) return align256(ira_workspace(g->ira, B, *p));
     return align256(generic_workspace(gargs(g), B, *p));
@@ -423,6 +433,7 @@ const char* ldpc_kernel_path(const ldpc_graph* g, const ldpc_params* p) {
     }
     if (layered_check(g, p) != LDPC_OK) return nullptr;
     if (use_lay(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc)) + "-layered";
+    else if (use_ira_lay(g, p)) path = "ira-z360-layered";
     else if (use_qc(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc));
     else if (use_ira(g, p)) path = "ira-z360";
     else path = "generic-csr";
@@ -492,6 +503,8 @@ static int decode_impl(const ldpc_graph* gc, const void* llr, int64_t B, const l
     int rc;
     if (use_lay(g, p)) {
         rc = qc_lay_decode(g->qc, llr_d, B, *p, bits_d, soft_d, used_d, st);
+    } else if (use_ira_lay(g, p)) {
+        rc = ira_lay_decode(g->ira, (const float*)llr_d, B, *p, bits_d, (float*)soft_d, used_d, ws, st);
     } else if (use_qc(g, p)) {
         rc = qc_decode(g->qc, llr_d, B, *p, bits_d, soft_d, used_d, ws, st);
     } else if (use_ira(g, p) && !w) {

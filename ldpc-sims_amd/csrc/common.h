@@ -497,4 +497,12 @@ bool ira_supports(const IRASpec* s, const ldpc_params& p);
 size_t ira_workspace(const IRASpec* s, int64_t B, const ldpc_params& p);
 int ira_decode(const IRASpec* s, const float* llr, int64_t B, const ldpc_params& p, uint8_t* bits, float* soft,
                int32_t* iters_used, char* ws, hipStream_t st);
+// Layered min-sum on the same graphs (ira_lay.hip, LDPC_F_LAYERED): fp32 min-sum while the information posteriors
+// fit a workgroup's LDS and no group meets a row more than twice; ira_lay_why names what rules a graph out (null:
+// nothing).  The workspace is per resident workgroup, not per codeword.
+bool ira_lay_supports(const IRASpec* s, const ldpc_params& p);
+const char* ira_lay_why(const IRASpec* s);
+size_t ira_lay_workspace(const IRASpec* s, int64_t B, const ldpc_params& p);
+int ira_lay_decode(const IRASpec* s, const float* llr, int64_t B, const ldpc_params& p, uint8_t* bits, float* soft,
+                   int32_t* iters_used, char* ws, hipStream_t st);
 }  // namespace ldpc

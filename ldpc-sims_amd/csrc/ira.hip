@@ -33,45 +33,9 @@
 #include <vector>
 
 #include "common.h"
+#include "ira_common.h"
 
 namespace ldpc {
-
-constexpr int kIZ = 360;       // DVB-S2 lifting (normal and short frames)
-constexpr int kIVS = 16;       // table stride: information-variable degree bound
-constexpr int kICS = 24;       // table stride: information slots per check bound
-constexpr int kIPS = 24;       // parity slots: kIPS (p_j) and kIPS + 1 (p_{j-1}); meta bits 0..25, argmin 27..31
-
-struct IRASpec {
-    int q = 0, G = 0, k = 0, n = 0, M = 0, E = 0, maxdv = 0, maxr = 0, device = 0;
-    int32_t *vn = nullptr, *vdeg = nullptr, *cn = nullptr, *cdeg = nullptr;  // device tables
-};
-
-// The tables are read-only for the whole decode: read through the constant address space so that every (uniform)
-// table read is a scalar load.  As plain global pointers the compiler could not rule out that the kernels' own stores
-// (app, states) alias them and read several rows with vector loads plus a wait and readfirstlane — one extra
-// dependent round trip per task (round 6).
-using cint32 = const __attribute__((address_space(4))) int32_t;
-struct IRADev {
-    cint32 *vn, *vdeg, *cn, *cdeg;
-    int q, G, k, n, M;
-};
-
-// One check's state, 12 bytes read and written as one dwordx3: the two output magnitudes and the meta word
-struct IraState {
-    float m1, m2;
-    uint32_t meta;
-};
-static_assert(sizeof(IraState) == 12, "one dwordx3 per check state");
-
-__device__ __forceinline__ IraState ira_ld_i(const IraState* __restrict__ base, int64_t i) { return base[i]; }
-__device__ __forceinline__ void ira_st_i(IraState* __restrict__ base, int64_t i, const IraState& s) { base[i] = s; }
-__device__ __forceinline__ IraState ira_ld(const IraState* __restrict__ p) { return *p; }
-
-// c2v of slot `slot` from a check state: the argmin slot gets mag2, every other mag1; sign bit from meta
-__device__ __forceinline__ float ira_c2v(const IraState& st, int slot) {
-    const float mag = ((st.meta >> 27) == (uint32_t)slot) ? st.m2 : st.m1;
-    return u2f(f2u(mag) | ((st.meta << (31 - slot)) & 0x80000000u));
-}
 
 // Workgroup b -> (codeword, task): blocks b and b + 8 share an XCD (MI355X_MICROARCH.md §Workgroup dispatch),
 // so the T tasks of a codeword get consecutive blocks of one XCD and its arrays stay in that XCD's L2 while
@@ -85,12 +49,11 @@ __device__ __forceinline__ bool ira_task(int T, int Bc, int& cw, int& task) {
     return cw < Bc;
 }
 
-// Workgroup shape: one task at a time over kIraLanes threads (6 waves over the 360 positions; lanes past 360
-// repeat the last position and store nothing), `tpw` tasks one after the other.  Every load of a task is issued
+// Workgroup shape: one task at a time over kIraLanes threads (ira_common.h: 6 waves over the 360 positions; lanes
+// past 360 repeat the last position and store nothing), `tpw` tasks one after the other.  Every load of a task is issued
 // before the first is used: a task waits on one memory round trip, not one per edge (A/B
 // profiles/r05/ab/ab_c4_ira_restructure.txt).  Two tasks side by side per workgroup measured no faster
 // (ab_c4_ira_tpp.txt), nor did several positions per lane (ab_c4_ira_ppl.txt).
-constexpr int kIraLanes = 384;
 // Fused parity posteriors: the check kernel forms the posterior of parity p(r, b) itself as soon as it has the new states of rows
 // r and r + 1 (consecutive rows of one workgroup: the row loop carries row r's new state to row r + 1), with the
 // variable kernel's operations, (L + c2v_r) + c2v_{r+1}; the variable kernel keeps only the parity rows that end a
@@ -493,6 +456,30 @@ IRASpec* ira_detect(int m, int n, const int32_t* rp, const int32_t* ci, int devi
         s->maxr = std::max(s->maxr, cdeg[a]);
         for (int i = 0; i < cdeg[a]; ++i) cn[(size_t)a * kICS + i] = rows[a][i].first | (rows[a][i].second << 8);
     }
+    // the layered schedule's view of the rows: a group that meets a row twice gives its variables two edges in
+    // that layer (ira_lay.hip); the second slot of such a pair finds the first by the pair's rank in the row
+    std::vector<int32_t> cnl(cn), clay(q, 0);
+    for (int a = 0; a < q && ok; ++a) {
+        int pairs = 0;
+        for (int i = 0; i < cdeg[a]; ++i) {
+            int first = -1, seen = 0;
+            for (int j = 0; j < i; ++j)
+                if (rows[a][j].first == rows[a][i].first) {
+                    if (first < 0) first = j;
+                    ++seen;
+                }
+            if (seen == 0) continue;
+            if (seen > 1) {  // (at most kICS / 2 = 12 pairs per row: the rank fits its 5 bits)
+                s->lay_pairs = -1;
+                continue;
+            }
+            cnl[(size_t)a * kICS + first] |= (1 << 17) | (pairs << 19);
+            cnl[(size_t)a * kICS + i] |= (2 << 17) | (pairs << 19);
+            ++pairs;
+        }
+        clay[a] = cdeg[a] | (pairs << 8);
+        if (s->lay_pairs >= 0) s->lay_pairs = std::max(s->lay_pairs, pairs);
+    }
     if (!ok) {
         delete s;
         return nullptr;
@@ -504,7 +491,8 @@ IRASpec* ira_detect(int m, int n, const int32_t* rp, const int32_t* ci, int devi
         if (hipMalloc((void**)d, h.size() * 4) != hipSuccess) return false;
         return hipMemcpy(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
     };
-    ok = up(&s->vn, vn) && up(&s->vdeg, vdeg) && up(&s->cn, cn) && up(&s->cdeg, cdeg);
+    ok = up(&s->vn, vn) && up(&s->vdeg, vdeg) && up(&s->cn, cn) && up(&s->cdeg, cdeg) && up(&s->cnl, cnl) &&
+         up(&s->clay, clay);
     if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     if (!ok) {
         ira_free(s);
@@ -519,6 +507,8 @@ void ira_free(IRASpec* s) {
     (void)hipFree(s->vdeg);
     (void)hipFree(s->cn);
     (void)hipFree(s->cdeg);
+    (void)hipFree(s->cnl);
+    (void)hipFree(s->clay);
     delete s;
 }
 

@@ -86,8 +86,8 @@ class Decoder:
                       int(app_max), float(qstep))
 
     def kernel_path(self, p: Params) -> str:
-        """The kernel family a decode with these params runs: "qc-z<Z>", "qc-z<Z>-layered", "ira-z360" or
-        "generic-csr"."""
+        """The kernel family a decode with these params runs: "qc-z<Z>", "qc-z<Z>-layered", "ira-z360",
+        "ira-z360-layered" or "generic-csr"."""
         s = self.lib.ldpc_kernel_path(self._h, ctypes.byref(p))
         if s is None:
             raise _abi.LdpcError(_abi.LDPC_EINVAL, self.lib.ldpc_last_error().decode(errors="replace"))
@@ -166,7 +166,8 @@ class Decoder:
         ``schedule``: "flooding" (default) or "layered" — row-serial min-sum (``LDPC_F_LAYERED`` in
         ``include/ldpc_abi.h``): float min-sum on the 802.11n codes with Z <= 64, about half the iterations of
         flooding for the same error rate, and quantized min-sum (``algo="qms"``) on (1296,2/3) while
-        ``app_max + 2*qmax <= 2047``; anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
+        ``app_max + 2*qmax <= 2047``; on IRA (DVB-S2) graphs float min-sum with one row of 360 checks per layer,
+        while the information bits fit a workgroup's LDS (DVB-S2 rate 1/2 does); anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
         is_torch = type(llr).__module__.startswith("torch")
         on_gpu = is_torch and llr.is_cuda
         fdt = np.float64 if precision == "f64" else np.float32

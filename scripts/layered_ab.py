@@ -2,7 +2,10 @@
 """A/B of the layered against the flooding schedule on bench.py's config [1] workload — (648,1/2) min-sum,
 B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — or, with --algo qms, on config [3]'s:
 (1296,2/3), 5-bit LLRs (qmax 15, app_max 127, --qstep), early stop (--early-stop), flooding-20 against layered-10;
---fixed-pair adds the same pair without early stop under "fixed_count".  In one process on one GPU:
+--fixed-pair adds the same pair without early stop under "fixed_count"; or, with --code dvbs2_12, on config [4]'s:
+DVB-S2 rate 1/2, B = 4,096, Eb/N0 0:0.5:2 dB, the two-stream flooding IRA kernels at 50 iterations against the
+LDS-resident layered IRA kernel at 25 sweeps (its record also carries the slot count and the time per layer of one
+workgroup).  In one process on one GPU:
 
   * block error rate of both legs at every Eb/N0 point (ldpc_count_errors), flooding at --flood-iters (50)
     and layered at --lay-iters (25);
@@ -13,6 +16,8 @@ B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — or, with 
     python scripts/layered_ab.py --out profiles/layered_ab.json [--pairs 12] [--launches 11]
     python scripts/layered_ab.py --algo qms --code wifi1296_23 --flood-iters 20 --lay-iters 10 --early-stop \
         --fixed-pair --out profiles/layered/ab_q5.json
+    python scripts/layered_ab.py --code dvbs2_12 --batch 4096 --ebn0 0:0.5:2 --pairs 10 --launches 5 --warmup 10 \
+        --out profiles/layered/ab_ira.json
 
 Needs a GPU; writes one JSON record.
 """
@@ -123,6 +128,13 @@ def main():
             out["legs"][nm].update(launch_ms_median=statistics.median(ms), launch_ms_min=min(ms), launch_ms_max=max(ms),
                                    ms_per_sweep=statistics.median(ms) / legs[nm]["iters"],
                                    cw_per_s=B / (statistics.median(ms) * 1e-3))
+        lay = legs["layered"]
+        if lay["kernel_path"] == "ira-z360-layered":  # one workgroup per slot decodes ceil(B / slots) codewords in turn
+            a256 = lambda v: (v + 255) // 256 * 256
+            slots = lay["wsb"] // (a256(12 * m) + a256(4 * m))
+            trips = -(-B // slots)
+            out["legs"]["layered"].update(slots=slots, codewords_per_slot=trips, us_per_layer=out["legs"]["layered"][
+                "launch_ms_median"] * 1e3 / (trips * lay["iters"] * (m // 360)))
         out["ratio_median"] = statistics.median(ratios)
         out["ratio_min"], out["ratio_max"] = min(ratios), max(ratios)
         return out, legs
