@@ -204,6 +204,53 @@ int ldpc_decode_weighted(const ldpc_graph* g, const void* llr, int64_t B, const 
                          const ldpc_bp_weights* w, uint8_t* bits_out, void* soft_out, int32_t* iters_used,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training: the gradient of the weighted tanh-SP forward above (the reference's hand-written autograd Functions,
+ * pytorch/bp/bp_vc.py:34-58 and bp_cv.py:57-96, on the GPU).  The differentiated function, in natural units:
+ *
+ *   L = -llr, x^0 = 0
+ *   for it in 0 .. iters-1, variable v with edge slots t, u:
+ *       s_t = 0.5 * (lw_it[v] * L_v + sum_{u != t} vn_it[t,u] * x_u),   tau_t = tanh(s_t)
+ *     check c with edges e:
+ *       p_e = prod_{e' != e} tau_e',  ph = clamp(p_e, +-(1 - 1e-7)),  x_e = clamp(log((1 + ph) / (1 - ph)), +-clamp)
+ *   z_v = 0.5 * (fin_llr[v] * L_v + sum_u fin[var_ptr[v] + u] * x_u);  soft = z (LDPC_F_SOFT_Z) or 1 - sigmoid(z)
+ *
+ * Given G = d loss / d soft [B][n], ldpc_bp_backward returns the mathematical gradient of that function with
+ * respect to vn [iters][W], the LLR weights [iters][n], fin [E], fin_llr [n] and llr [B][n].
+ *   - A message whose magnitude was limited by either bound passes no gradient (torch.clamp's rule away from
+ *     equality); the bound is min(clamp, log((1 + pmax) / (1 - pmax))), pmax = 1 - 1e-7, in fp64 and the merged
+ *     log2-unit bound of the fp32 kernels (min(fp32(clamp * log2 e), 24)) in fp32.  The reference's own CV
+ *     backward is straight-through at the p clamp and is NOT followed.
+ *   - d p_e / d tau_u is formed from exclusive products, never by dividing by tau, so an exact-zero tau (an
+ *     exact-zero LLR at iteration 0) needs no special case.
+ *   - vn[0] (x^0 = 0) and the diagonal compact positions (u == t) have exactly zero gradient.
+ *   - LDPC_F_EARLY_STOP, any algo but LDPC_ALGO_TANH_SP, and initial messages are LDPC_EUNSUPPORTED; iters >= 1.
+ *   - fp32 and fp64 (LDPC_F_F64).  The result is bitwise reproducible: no floating-point atomics, the batch is
+ *     reduced in a fixed order.
+ *   - The vn gradient needs every variable degree <= 16 (one MFMA tile); a larger degree is LDPC_EUNSUPPORTED
+ *     when out->vn is wanted, and the other gradients are still served.
+ *
+ * The tape holds L [n][ldb], every iteration's v2c [E][ldb] and c2v [E][ldb] as the generic kernels store them
+ * (codeword-minor, ldb = B rounded up to 64; fp32: v2c = +-e^{-|2s|} and c2v in log2 units) and one zero-LLR flag
+ * per codeword: elem * ldb * (n + 2 * E * iters) + ldb bytes.  ldpc_bp_forward_tape runs the kernels of
+ * ldpc_decode_weighted on the tape's slices, so its soft_out is bitwise that function's.  All pointers are DEVICE
+ * pointers (LDPC_F_DEVICE_PTRS is implied) and every call is asynchronous on stream; w may be NULL (all ones).
+ * ldpc_bp_grads: NULL = not wanted; each wanted array is overwritten. */
+typedef struct ldpc_bp_grads {
+    void* vn;
+    void* llr_w;
+    void* fin;
+    void* fin_llr;
+    void* llr;
+} ldpc_bp_grads;
+
+int ldpc_bp_tape_size(const ldpc_graph* g, int64_t B, const ldpc_params* p, size_t* tape_bytes,
+                      size_t* backward_ws_bytes);
+int ldpc_bp_forward_tape(const ldpc_graph* g, const void* llr, int64_t B, const ldpc_params* p,
+                         const ldpc_bp_weights* w, void* soft_out, void* tape, size_t tape_bytes, void* stream);
+int ldpc_bp_backward(const ldpc_graph* g, int64_t B, const ldpc_params* p, const ldpc_bp_weights* w,
+                     const void* tape, size_t tape_bytes, const void* grad_soft, const ldpc_bp_grads* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* BeliefPropagation.forward(x, llr, clamp) with NON-ZERO initial messages x (pytorch/bp/bp.py:43-47: the
  * first layer consumes x exactly as later layers consume the previous c2v).  x0: DEVICE [B][E] in the
  * reference's check-order edge numbering (masking.py:84-88), element type = the decode precision; NULL =

@@ -19,7 +19,8 @@ SRCS = [("abi.hip", "abi.hip.o", []), ("generic.hip", "generic.hip.o", [])] + [
            ("qc_sl_es.hip", "qc_sl_es.hip.o", []), ("qc_es.hip", "qc_es.hip.o", []),
            ("qc_lay.hip", "qc_lay.hip.o", []), ("qc_lay_pk.hip", "qc_lay_pk.hip.o", []),
            ("channel.hip", "channel.hip.o", []), ("ira.hip", "ira.hip.o", []), ("ira_lay.hip", "ira_lay.hip.o", []),
-           ("encode.hip", "encode.hip.o", []), ("aux_streams.hip", "aux_streams.hip.o", [])]
+           ("encode.hip", "encode.hip.o", []), ("aux_streams.hip", "aux_streams.hip.o", []),
+           ("bp_grad.hip", "bp_grad.hip.o", [])]
 OUT = os.path.join(HERE, "ldpc_amd", "libldpc_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off",  # min-sum must round exactly like oracle/ldpc_oracle.c (no FMA contraction)

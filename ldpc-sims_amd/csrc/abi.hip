@@ -551,6 +551,60 @@ int ldpc_decode_weighted(const ldpc_graph* g, const void* llr, int64_t B, const 
     return decode_impl(g, llr, B, &q, bits_out, soft_out, iters_used, workspace, workspace_bytes, stream, &bw);
 }
 
+// Training (bp_grad.hip): what the three entry points share — the params a tape is defined for
+static int bp_grad_check(const ldpc_graph* g, int64_t B, const ldpc_params* p) {
+    if (!g) return set_error(LDPC_EINVAL, "null graph");
+    if (!p || !params_valid(p)) return set_error(LDPC_EINVAL, "invalid ldpc_params");
+    if (p->algo != LDPC_ALGO_TANH_SP)
+        return set_error(LDPC_EUNSUPPORTED, "the differentiable decoder is tanh sum-product only (algo %d asked)", p->algo);
+    if (p->flags & LDPC_F_EARLY_STOP)
+        return set_error(LDPC_EUNSUPPORTED, "LDPC_F_EARLY_STOP (early stop) has no gradient: the tape holds a fixed iteration count");
+    if (p->flags & LDPC_F_LAYERED)
+        return set_error(LDPC_EUNSUPPORTED, "LDPC_F_LAYERED is not implemented for the differentiable decoder");
+    if (p->iters < 1) return set_error(LDPC_EINVAL, "the differentiable decoder needs iters >= 1");
+    if (B < 1) return set_error(LDPC_EINVAL, "B < 1");
+    return LDPC_OK;
+}
+
+int ldpc_bp_tape_size(const ldpc_graph* g, int64_t B, const ldpc_params* p, size_t* tape_bytes,
+                      size_t* backward_ws_bytes) {
+    if (const int rc = bp_grad_check(g, B, p)) return rc;
+    if (tape_bytes) *tape_bytes = bp_tape_layout(g->n, g->E, B, elem_size(p), p->iters).total;
+    if (backward_ws_bytes) *backward_ws_bytes = bp_backward_workspace(gargs(g), B, *p);
+    return LDPC_OK;
+}
+
+static BPWeights bp_weights(const ldpc_bp_weights* w) {
+    return BPWeights{w ? w->vn : nullptr, w ? w->llr : nullptr, w ? w->fin : nullptr, w ? w->fin_llr : nullptr};
+}
+
+int ldpc_bp_forward_tape(const ldpc_graph* g, const void* llr, int64_t B, const ldpc_params* p,
+                         const ldpc_bp_weights* w, void* soft_out, void* tape, size_t tape_bytes, void* stream) {
+    if (const int rc = bp_grad_check(g, B, p)) return rc;
+    if (!llr || !tape) return set_error(LDPC_EINVAL, "llr or tape is null");
+    const size_t need = bp_tape_layout(g->n, g->E, B, elem_size(p), p->iters).total;
+    if (tape_bytes < need) return set_error(LDPC_ENOMEM, "tape %zu bytes < required %zu", tape_bytes, need);
+    DeviceGuard dg(g->device);
+    BPWeights bw = bp_weights(w);
+    bw.tape = (char*)tape;
+    return generic_forward_tape(gargs(g), llr, B, *p, soft_out, (hipStream_t)stream, bw);
+}
+
+int ldpc_bp_backward(const ldpc_graph* g, int64_t B, const ldpc_params* p, const ldpc_bp_weights* w,
+                     const void* tape, size_t tape_bytes, const void* grad_soft, const ldpc_bp_grads* out,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = bp_grad_check(g, B, p)) return rc;
+    if (!tape || !grad_soft || !out || !workspace) return set_error(LDPC_EINVAL, "tape, grad_soft, out or workspace is null");
+    const size_t need = bp_tape_layout(g->n, g->E, B, elem_size(p), p->iters).total;
+    if (tape_bytes < need) return set_error(LDPC_ENOMEM, "tape %zu bytes < required %zu", tape_bytes, need);
+    const size_t need_ws = bp_backward_workspace(gargs(g), B, *p);
+    if (workspace_bytes < need_ws)
+        return set_error(LDPC_ENOMEM, "workspace %zu bytes < required %zu", workspace_bytes, need_ws);
+    DeviceGuard dg(g->device);
+    return bp_backward(gargs(g), B, *p, bp_weights(w), (const char*)tape, grad_soft, *out, (char*)workspace,
+                       (hipStream_t)stream);
+}
+
 int ldpc_decode_x0(const ldpc_graph* g, const void* llr, int64_t B, const ldpc_params* p, const ldpc_bp_weights* w,
                    const void* x0, uint8_t* bits_out, void* soft_out, int32_t* iters_used, void* workspace,
                    size_t workspace_bytes, void* stream) {

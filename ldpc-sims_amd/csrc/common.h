@@ -440,10 +440,37 @@ struct GenericArgs {
 struct BPWeights {
     const void *vn, *lw, *fin, *flw;
     const void* c2v0 = nullptr;  // initial c2v [B][E] check-order (the reference's x, bp/bp.py:43-47); NULL = 0
+    char* tape = nullptr;        // ldpc_bp_forward_tape: L, every iteration's v2c / c2v and the zero flags go here
 };
+// The tape of a differentiable forward (bp_grad.hip reads it back): L [n][ldb], then per iteration v2c [E][ldb]
+// and c2v [E][ldb] exactly as the generic kernels store them (fp32: signed a and log2-unit c2v), then one
+// zero-LLR flag byte per codeword.  ldb = B rounded up to 64, so every slice is 256-byte aligned.
+struct BPTape {
+    int64_t ldb;
+    size_t L, msg, slice, zf, total;  // iteration it: v2c at msg + 2 it slice, c2v one slice further
+    size_t v2c(int it) const { return msg + (size_t)2 * it * slice; }
+    size_t c2v(int it) const { return v2c(it) + slice; }
+};
+inline BPTape bp_tape_layout(int n, int E, int64_t B, size_t elem, int iters) {
+    BPTape t{};
+    t.ldb = (B + 63) / 64 * 64;
+    t.L = 0;
+    t.msg = elem * (size_t)t.ldb * n;
+    t.slice = elem * (size_t)t.ldb * E;
+    t.zf = t.msg + (size_t)2 * iters * t.slice;
+    t.total = t.zf + (size_t)t.ldb;
+    return t;
+}
 size_t generic_workspace(const GenericArgs& g, int64_t B, const ldpc_params& p);
 int generic_decode(const GenericArgs& g, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits,
                    void* soft, int32_t* iters_used, char* ws, hipStream_t st, const BPWeights* w = nullptr);
+// Differentiable weighted tanh-SP (ldpc_bp_forward_tape / ldpc_bp_backward).  The forward is the generic driver
+// writing into w.tape (generic.hip); the backward kernels are bp_grad.hip.  Device pointers, asynchronous on st.
+int generic_forward_tape(const GenericArgs& g, const void* llr_dev, int64_t B, const ldpc_params& p, void* soft,
+                         hipStream_t st, const BPWeights& w);
+size_t bp_backward_workspace(const GenericArgs& g, int64_t B, const ldpc_params& p);
+int bp_backward(const GenericArgs& g, int64_t B, const ldpc_params& p, const BPWeights& w, const char* tape,
+                const void* grad_soft, const ldpc_bp_grads& out, char* ws, hipStream_t st);
 
 // Structure-specialised (quasi-cyclic) decoders compiled into the library (qc.hip).
 struct QCSpec;

@@ -44,6 +44,18 @@ int generic_decode(const GenericArgs& g, const void* llr_dev, int64_t B, const l
     return LDPC_OK;
 }
 
+// The differentiable forward: the weighted tanh-SP driver in one pass (a tape is never chunked) with its message
+// buffers on w.tape, so it needs no workspace.
+int generic_forward_tape(const GenericArgs& g, const void* llr_dev, int64_t B, const ldpc_params& p, void* soft,
+                         hipStream_t st, const BPWeights& w) {
+    const int rc = (p.flags & LDPC_F_F64) ? generic_run_sp64(g, llr_dev, B, p, nullptr, soft, nullptr, nullptr, st, &w)
+                                          : generic_run_sp32(g, llr_dev, B, p, nullptr, soft, nullptr, nullptr, st, &w);
+    if (rc != LDPC_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(LDPC_EHIP, "tape forward launch: %s", hipGetErrorString(e));
+    return LDPC_OK;
+}
+
 static int decode_chunk(const GenericArgs& g, const void* llr_dev, int64_t B, const ldpc_params& p, uint8_t* bits,
                         void* soft, int32_t* iters_used, char* ws, hipStream_t st, const BPWeights* w) {
     const bool es = (p.flags & LDPC_F_EARLY_STOP) != 0;

@@ -660,9 +660,14 @@ static int run(const GenericArgs& g, const T* llr_dev, int64_t B, const ldpc_par
                int32_t* iters_used, char* ws, hipStream_t st, const BPWeights* wts) {
     const int64_t ldb = (B + 63) / 64 * 64;
     const WsLayout w = layout(g, B, sizeof(T), ES);
-    T* L = (T*)(ws + w.L);
-    T* v2c = (T*)(ws + w.v2c);
-    T* c2v = (T*)(ws + w.c2v);
+    // a differentiable forward (wts->tape, common.h BPTape) keeps L, every iteration's messages and the zero
+    // flags on the tape instead of the workspace's ping-pong buffers: same kernels, same tiles, same results
+    char* tape = wts ? wts->tape : nullptr;
+    const BPTape tl = bp_tape_layout(g.n, g.E, B, sizeof(T), p.iters);
+    T* L = tape ? (T*)(tape + tl.L) : (T*)(ws + w.L);
+    T* v2c = tape ? nullptr : (T*)(ws + w.v2c);
+    T* c2v = tape ? nullptr : (T*)(ws + w.c2v);
+    const T* c2v_in = c2v;  // what the VN kernel reads: the previous iteration's c2v
     uint8_t* hb = ES ? (uint8_t*)(ws + w.hb) : nullptr;
     uint8_t* done = ES ? (uint8_t*)(ws + w.done) : nullptr;
     uint8_t* unsat = ES ? (uint8_t*)(ws + w.unsat) : nullptr;
@@ -673,7 +678,7 @@ static int run(const GenericArgs& g, const T* llr_dev, int64_t B, const ldpc_par
     const unsigned gcw = (unsigned)((B + kTB - 1) / kTB);
     const T unit = (!MS && std::is_same_v<T, float>) ? T(kLog2eF32) : T(1);  // fp32 tanh-SP messages: log2 units
     k_load_llr<T><<<dim3((unsigned)((B + 63) / 64), (g.n + 63) / 64), tb, 0, st>>>(llr_dev, L, B, g.n, ldb, T(-1));
-    uint8_t* zf = (uint8_t*)(ws + w.zf);
+    uint8_t* zf = tape ? (uint8_t*)(tape + tl.zf) : (uint8_t*)(ws + w.zf);
     if constexpr (!MS && std::is_same_v<T, float>)
         k_zero_flags<><<<(unsigned)((B + 3) / 4), tb, 0, st>>>((const float*)llr_dev, B, g.n, zf);
     // non-zero initial messages x (bp/bp.py:43-47): iteration 0 reads them like any later iteration
@@ -702,11 +707,16 @@ static int run(const GenericArgs& g, const T* llr_dev, int64_t B, const ldpc_par
     };
     for (int it = 0; it < p.iters; ++it) {
         const int first = (it == 0) && !x0;
+        if (tape) {
+            v2c = (T*)(tape + tl.v2c(it));
+            c2v_in = it ? (const T*)(tape + tl.c2v(it - 1)) : nullptr;  // first: not read
+            c2v = (T*)(tape + tl.c2v(it));
+        }
         if (!MS && wts && (wts->vn || wts->lw)) {
             const T* vn_it = w_vn ? w_vn + (int64_t)it * g.W : nullptr;
             const T* lw_it = w_lw ? w_lw + (int64_t)it * g.n : nullptr;
 #define VNW1(D, VV) \
-    k_vn_spw<T, D, VV><<<grid(VV, tpl2, g.n), tb, 0, st>>>(g.var_ptr, g.var_edges, g.wofs, vn_it, lw_it, L, c2v, v2c, B, ldb, first, g.n, tpl2)
+    k_vn_spw<T, D, VV><<<grid(VV, tpl2, g.n), tb, 0, st>>>(g.var_ptr, g.var_edges, g.wofs, vn_it, lw_it, L, c2v_in, v2c, B, ldb, first, g.n, tpl2)
 #define VNW(D)                                                     \
     do {                                                           \
         int V, tpl2;                                               \
@@ -721,9 +731,9 @@ static int run(const GenericArgs& g, const T* llr_dev, int64_t B, const ldpc_par
     do {                                                                                                           \
         if constexpr (MS)                                                                                          \
             k_vn_ms<D, ES, VV><<<grid(VV, tpl2, g.n), tb, 0, st>>>(g.var_ptr, g.var_edges, (const float*)L,          \
-                (const float*)c2v, (float*)v2c, B, ldb, first, hb, done, g.n, tpl2);                              \
+                (const float*)c2v_in, (float*)v2c, B, ldb, first, hb, done, g.n, tpl2);                              \
         else                                                                                                       \
-            k_vn_sp<T, D, ES, VV><<<grid(VV, tpl2, g.n), tb, 0, st>>>(g.var_ptr, g.var_edges, L, c2v, v2c,          \
+            k_vn_sp<T, D, ES, VV><<<grid(VV, tpl2, g.n), tb, 0, st>>>(g.var_ptr, g.var_edges, L, c2v_in, v2c,       \
                 B, ldb, first, hb, done, g.n, tpl2);                                                               \
     } while (0)
 #define VN(D)                                                      \

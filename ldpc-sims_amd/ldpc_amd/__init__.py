@@ -8,12 +8,12 @@ from .codes import Encoder, Graph, QCCode, get_code, peg_64_32, qc_expand, wifi_
 
 _abi.load()  # fail loudly at import if the HIP library is missing: there is no CPU fallback
 
-__all__ = ["Decoder", "decode", "decode_bits", "decoder", "encode", "get_decoder", "BeliefPropagation", "codes",
+__all__ = ["Decoder", "decode", "decode_bits", "decoder", "encode", "get_decoder", "BeliefPropagation", "WeightedBP", "codes",
            "Encoder", "Graph", "QCCode", "get_code", "peg_64_32", "qc_expand", "wifi_code"]
 
 
 def __getattr__(name):
-    if name == "BeliefPropagation":
+    if name in ("BeliefPropagation", "WeightedBP"):
         from . import api
-        return api.BeliefPropagation
+        return getattr(api, name)
     raise AttributeError(name)

@@ -23,6 +23,7 @@ EXPORTS = (
     "ldpc_random_bits", "ldpc_ofdm_tx", "ldpc_ofdm_demod", "ldpc_adc_quantize", "ldpc_weights_layout",
     "ldpc_decode_weighted", "ldpc_decode_x0", "ldpc_decode_bits_host", "ldpc_last_error", "ldpc_device_count",
     "ldpc_version", "ldpc_kernel_path", "ldpc_abi_version", "ldpc_encode", "ldpc_encoder_path",
+    "ldpc_bp_tape_size", "ldpc_bp_forward_tape", "ldpc_bp_backward",
 )
 ABI_VERSION = 2  # LDPC_ABI_VERSION of include/ldpc_abi.h this binding is written for
 
@@ -45,6 +46,12 @@ class BPWeights(ctypes.Structure):
     """ldpc_bp_weights: device pointers (vn, llr, fin, fin_llr), NULL = all ones."""
     _fields_ = [("vn", ctypes.c_void_p), ("llr", ctypes.c_void_p), ("fin", ctypes.c_void_p),
                 ("fin_llr", ctypes.c_void_p)]
+
+
+class BPGrads(ctypes.Structure):
+    """ldpc_bp_grads: device pointers the backward overwrites, NULL = not wanted."""
+    _fields_ = [("vn", ctypes.c_void_p), ("llr_w", ctypes.c_void_p), ("fin", ctypes.c_void_p),
+                ("fin_llr", ctypes.c_void_p), ("llr", ctypes.c_void_p)]
 
 
 _lib = None
@@ -95,10 +102,15 @@ def load(path: str | None = None):
     L.ldpc_decode_x0.argtypes = [vp, vp, i64, ctypes.POINTER(Params), ctypes.POINTER(BPWeights), vp, vp, vp, vp,
                                  vp, sz, vp]
     L.ldpc_decode_bits_host.argtypes = [vp, vp, i64, ctypes.POINTER(Params), vp, i64, i32]
+    L.ldpc_bp_tape_size.argtypes = [vp, i64, ctypes.POINTER(Params), ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    L.ldpc_bp_forward_tape.argtypes = [vp, vp, i64, ctypes.POINTER(Params), ctypes.POINTER(BPWeights), vp, vp, sz, vp]
+    L.ldpc_bp_backward.argtypes = [vp, i64, ctypes.POINTER(Params), ctypes.POINTER(BPWeights), vp, sz, vp,
+                                   ctypes.POINTER(BPGrads), vp, sz, vp]
     for f in ("ldpc_graph_create", "ldpc_graph_create_qc", "ldpc_graph_destroy", "ldpc_graph_info",
               "ldpc_workspace_size", "ldpc_decode_ex", "ldpc_decode", "ldpc_count_errors", "ldpc_awgn_llr",
               "ldpc_random_bits", "ldpc_ofdm_tx", "ldpc_ofdm_demod", "ldpc_adc_quantize", "ldpc_weights_layout", "ldpc_decode_weighted",
-              "ldpc_decode_x0", "ldpc_decode_bits_host", "ldpc_device_count", "ldpc_abi_version", "ldpc_encode"):
+              "ldpc_decode_x0", "ldpc_decode_bits_host", "ldpc_device_count", "ldpc_abi_version", "ldpc_encode",
+              "ldpc_bp_tape_size", "ldpc_bp_forward_tape", "ldpc_bp_backward"):
         getattr(L, f).restype = ctypes.c_int
     L.ldpc_last_error.restype = ctypes.c_char_p
     L.ldpc_version.restype = ctypes.c_char_p

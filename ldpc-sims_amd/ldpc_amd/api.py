@@ -251,6 +251,98 @@ class Decoder:
         return dict(bits=bits, soft=sft, iters_used=used)
 
 
+    # ---- training: the differentiable weighted tanh-SP (ldpc_bp_forward_tape / ldpc_bp_backward) --------------
+    def _stream(self, stream, dev):
+        torch = _torch()
+        cur = torch.cuda.current_stream(dev)
+        ext = cur if stream is None else stream
+        if isinstance(ext, int) and not isinstance(ext, bool):  # a raw hipStream_t handle
+            ext = torch.cuda.ExternalStream(ext, device=dev)
+        if not isinstance(ext, torch.cuda.Stream):
+            raise TypeError("stream must be a torch.cuda.Stream, an int stream handle, or None (current stream)")
+        return cur, ext
+
+    def bp_forward(self, llr, iters: int, weights=None, clamp=10.0, soft="p1", precision="f32", stream=None, *,
+                   algo="tanh", early_stop=False, x0=None):
+        """The weighted tanh-SP forward of ``decode(weights=...)`` that also keeps a tape for ``bp_backward``:
+        ``(soft, tape)`` with ``soft`` (B, n) = p1 or z, bitwise what ``decode`` returns for the same inputs.
+        torch GPU tensors only; ``stream`` as in ``decode``.  The tape holds every iteration's messages
+        (``tape.nbytes``: elem * ldb * (n + 2 E iters)) and the weights it was run with; it is consumed, any number
+        of times, by ``bp_backward`` on the same stream.  Only tanh-SP with a fixed iteration count and zero
+        initial messages is differentiable: ``algo``, ``early_stop`` and ``x0`` exist to say so
+        (``LDPC_EUNSUPPORTED``)."""
+        torch = _torch()
+        if not (type(llr).__module__.startswith("torch") and llr.is_cuda):
+            raise ValueError("bp_forward needs a torch GPU tensor")
+        if llr.device.index != self.device:
+            raise ValueError(f"llr is on {llr.device}, this decoder's graph is on cuda:{self.device}")
+        if x0 is not None:
+            raise _abi.LdpcError(_abi.LDPC_EUNSUPPORTED, "initial messages (x0) are not differentiable here: the "
+                                 "tape forward starts from x = 0")
+        p = self.params(iters, algo, clamp, early_stop=early_stop, precision=precision, soft=soft,
+                        force_generic=True, device_ptrs=True)
+        tb, wb = ctypes.c_size_t(), ctypes.c_size_t()
+        wstruct, wkeep = self.device_weights(weights, iters, precision)
+        cur, ext = self._stream(stream, llr.device)
+        if ext != cur:
+            ext.wait_stream(cur)
+            for t in [llr] + wkeep:
+                t.record_stream(ext)
+        tdt = torch.float64 if precision == "f64" else torch.float32
+        with torch.cuda.stream(ext):
+            x = llr.detach().to(tdt).contiguous()
+            if x.dim() != 2 or x.shape[1] != self.n:
+                raise RuntimeError(f"llr must be (B, {self.n}), got {tuple(x.shape)}")
+            B = x.shape[0]
+            check(self.lib.ldpc_bp_tape_size(self._h, B, ctypes.byref(p), ctypes.byref(tb), ctypes.byref(wb)))
+            buf = torch.empty((tb.value,), dtype=torch.uint8, device=x.device)
+            sft = torch.empty((B, self.n), dtype=tdt, device=x.device)
+            check(self.lib.ldpc_bp_forward_tape(self._h, x.data_ptr(), B, ctypes.byref(p), ctypes.byref(wstruct),
+                                                sft.data_ptr(), buf.data_ptr(), tb.value,
+                                                ctypes.c_void_p(ext.cuda_stream)))
+        return sft, BPTape(buf, B, p, wstruct, wkeep, tdt, wb.value, ext)
+
+    def bp_backward(self, tape, grad_soft, want=("vn", "llr_w", "fin", "fin_llr", "llr")):
+        """Gradients of ``loss`` given ``grad_soft = d loss / d soft`` (B, n): dict of ``vn`` (iters, W), ``llr_w``
+        (iters, n), ``fin`` (E,), ``fin_llr`` (n,), ``llr`` (B, n) for the names in ``want``, in the tape's
+        precision, on the tape's stream.  The mathematical gradient of the decoder (include/ldpc_abi.h): a clamped
+        message passes none; bitwise reproducible.  ``vn`` needs every variable degree <= 16."""
+        torch = _torch()
+        bad = set(want) - {"vn", "llr_w", "fin", "fin_llr", "llr"}
+        if bad:
+            raise ValueError(f"unknown gradient names {sorted(bad)}")
+        iters, dev = tape.params.iters, tape.buf.device
+        shapes = dict(vn=(iters, self.weights_per_iter), llr_w=(iters, self.n), fin=(self.E,), fin_llr=(self.n,),
+                      llr=(tape.B, self.n))
+        cur = torch.cuda.current_stream(dev)
+        if tape.stream != cur:
+            tape.stream.wait_stream(cur)
+            grad_soft.record_stream(tape.stream)
+        with torch.cuda.stream(tape.stream):
+            G = grad_soft.detach().to(device=dev, dtype=tape.dtype).contiguous()
+            if tuple(G.shape) != (tape.B, self.n):
+                raise RuntimeError(f"grad_soft must be ({tape.B}, {self.n}), got {tuple(G.shape)}")
+            out = {k: torch.empty(shapes[k], dtype=tape.dtype, device=dev) for k in shapes if k in want}
+            gs = _abi.BPGrads(*[out[k].data_ptr() if k in out else None for k in ("vn", "llr_w", "fin", "fin_llr", "llr")])
+            ws = torch.empty((max(tape.ws_bytes, 1),), dtype=torch.uint8, device=dev)
+            check(self.lib.ldpc_bp_backward(self._h, tape.B, ctypes.byref(tape.params), ctypes.byref(tape.wstruct),
+                                            tape.buf.data_ptr(), tape.buf.numel(), G.data_ptr(), ctypes.byref(gs),
+                                            ws.data_ptr(), tape.ws_bytes, ctypes.c_void_p(tape.stream.cuda_stream)))
+        return out
+
+
+class BPTape:
+    """What ``Decoder.bp_forward`` leaves for ``bp_backward``: the message tape and what it was made with."""
+
+    def __init__(self, buf, B, params, wstruct, wkeep, dtype, ws_bytes, stream):
+        self.buf, self.B, self.params, self.wstruct, self.wkeep = buf, B, params, wstruct, wkeep
+        self.dtype, self.ws_bytes, self.stream = dtype, ws_bytes, stream
+
+    @property
+    def nbytes(self) -> int:
+        return self.buf.numel()
+
+
 _cache: dict = {}
 _cache_lock = threading.Lock()
 
@@ -489,13 +581,97 @@ def _make_bp_module():
     return BeliefPropagation
 
 
+def _make_weighted_bp():
+    torch = _torch()
+    nn = torch.nn
+    names = ("vn", "llr_w", "fin", "fin_llr", "llr")
+
+    class _BPFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, dec, iters, clamp, soft, precision, llr, vn, llr_w, fin, fin_llr):
+            sft, ctx.tape = dec.bp_forward(llr, iters, dict(vn=vn, llr=llr_w, fin=fin, fin_llr=fin_llr), clamp, soft,
+                                           precision)
+            ctx.dec = dec
+            return sft
+
+        @staticmethod
+        def backward(ctx, grad):
+            need = dict(zip(("llr", "vn", "llr_w", "fin", "fin_llr"), ctx.needs_input_grad[5:]))
+            g = ctx.dec.bp_backward(ctx.tape, grad, want=[k for k in names if need[k]])
+            return (None,) * 5 + tuple(g.get(k) for k in ("llr", "vn", "llr_w", "fin", "fin_llr"))
+
+    class WeightedBP(nn.Module):
+        """Trainable weighted ("neural") belief propagation on the GPU: the reference's ``BeliefPropagation``
+        with its VC weights as compact ``nn.Parameter``s — ``vn`` (iters, W), ``llr_weight`` (iters, n), ``fin``
+        (E,), ``fin_llr`` (n,), the layout of ``Graph.compact_weights``, all ones at first.  ``forward(llr)`` (a
+        GPU tensor, (B, n), log P1/P0) returns ``soft`` (p1 or z) and is differentiable in the parameters and in
+        ``llr``: forward and backward are the HIP kernels behind ``Decoder.bp_forward`` / ``bp_backward``.
+        ``.double()`` selects fp64.  The gradient is the mathematical one (a clamped message passes none), not
+        the reference's hand-written backward, which is straight-through at its p clamp."""
+
+        def __init__(self, H, iterations, clamp=10.0, soft="p1", device=0):
+            super().__init__()
+            self.H = H if isinstance(H, SparseCode) else np.asarray(H)
+            self.iterations, self.clamp, self.soft, self.device = int(iterations), float(clamp), soft, int(device)
+            self.graph = g = Graph.from_H(self.H)
+            dev = torch.device("cuda", self.device)
+            W = int(g.weight_offsets()[-1])
+            self.vn = nn.Parameter(torch.ones(self.iterations, W, device=dev))
+            self.llr_weight = nn.Parameter(torch.ones(self.iterations, g.n, device=dev))
+            self.fin = nn.Parameter(torch.ones(g.E, device=dev))
+            self.fin_llr = nn.Parameter(torch.ones(g.n, device=dev))
+
+        def forward(self, llr):
+            precision = "f64" if self.vn.dtype == torch.float64 else "f32"
+            return _BPFunction.apply(get_decoder(self.H, self.device), self.iterations, self.clamp, self.soft,
+                                     precision, llr, self.vn, self.llr_weight, self.fin, self.fin_llr)
+
+        def weights_dict(self):
+            """The weights as ``Decoder.decode(weights=...)`` takes them."""
+            return dict(vn=self.vn.detach(), llr=self.llr_weight.detach(), fin=self.fin.detach(),
+                        fin_llr=self.fin_llr.detach())
+
+        def load_reference_state_dict(self, sd):
+            """Weights from a reference ``BeliefPropagation.state_dict()``, as on ``BeliefPropagation``."""
+            it = range(self.iterations)
+            cvt = lambda a: a.detach().cpu().double().numpy()  # noqa: E731
+            c = self.graph.compact_weights([cvt(sd[f"layers.{i}.0.input_weight"]) for i in it],
+                                           [cvt(sd[f"layers.{i}.0.llr_weight"]) for i in it],
+                                           cvt(sd["final_layer.0.input_weight"]), cvt(sd["final_layer.0.llr_weight"]))
+            with torch.no_grad():
+                for prm, k in ((self.vn, "vn"), (self.llr_weight, "llr"), (self.fin, "fin"), (self.fin_llr, "fin_llr")):
+                    prm.copy_(torch.from_numpy(c[k]).to(prm))
+            return self
+
+        def reference_state_dict(self):
+            """The weights in the reference module's dense layout and key names (``Graph.dense_weights``), so
+            that trained weights load into the reference (and into ``BeliefPropagation.load_reference_state_dict``)."""
+            w = {k: v.cpu().double().numpy() for k, v in self.weights_dict().items()}
+            dn = self.graph.dense_weights(w["vn"], w["llr"], w["fin"], w["fin_llr"])
+            dt = self.vn.dtype
+            sd = {}
+            for i in range(self.iterations):
+                sd[f"layers.{i}.0.input_weight"] = torch.from_numpy(dn["input_weights"][i]).to(dt)
+                sd[f"layers.{i}.0.llr_weight"] = torch.from_numpy(dn["llr_weights"][i]).to(dt)
+            sd["final_layer.0.input_weight"] = torch.from_numpy(dn["final_input_weight"]).to(dt)
+            sd["final_layer.0.llr_weight"] = torch.from_numpy(dn["final_llr_weight"]).to(dt)
+            return sd
+
+    return WeightedBP
+
+
 _BP = None
+_WBP = None
 
 
 def __getattr__(name):  # lazy so that importing ldpc_amd does not import torch
-    global _BP
+    global _BP, _WBP
     if name == "BeliefPropagation":
         if _BP is None:
             _BP = _make_bp_module()
         return _BP
+    if name == "WeightedBP":
+        if _WBP is None:
+            _WBP = _make_weighted_bp()
+        return _WBP
     raise AttributeError(name)

@@ -275,6 +275,23 @@ class Graph:
             out["fin_llr"] = np.asarray(final_llr_weight, np.float64).reshape(-1)
         return out
 
+    def dense_weights(self, vn, llr, fin, fin_llr):
+        """The inverse of ``compact_weights``: compact vn [iters][W], llr [iters][n], fin [E], fin_llr [n] -> dict
+        of ``input_weights`` (per iteration E x E), ``llr_weights`` (per iteration (1, n)), ``final_input_weight``
+        (n x E) and ``final_llr_weight`` (1, n) in the reference's layout.  Positions outside the masks (and the
+        compact diagonal, which is no weight) are zero, as the reference's masked initialisation leaves them."""
+        tgt, src, pos = self.vn_weight_index()
+        vn = np.asarray(vn, np.float64)
+        iw = []
+        for row in vn:
+            w = np.zeros((self.E, self.E))
+            w[tgt, src] = row[pos]
+            iw.append(w)
+        fw = np.zeros((self.n, self.E))
+        fw[np.repeat(np.arange(self.n), self.var_degrees()), self.var_edges] = np.asarray(fin, np.float64)
+        return dict(input_weights=iw, llr_weights=[np.asarray(r, np.float64).reshape(1, -1) for r in np.asarray(llr)],
+                    final_input_weight=fw, final_llr_weight=np.asarray(fin_llr, np.float64).reshape(1, -1))
+
 
 # ---------------------------------------------------------------------------------------------
 def _gf2_solve_right(B: np.ndarray, A: np.ndarray) -> np.ndarray:
