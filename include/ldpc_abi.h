@@ -109,8 +109,28 @@ enum {
  * cannot change a value.  Implemented for the compiled codes with 32 < Z <= 64 ((1296,2/3)) in packed fp16, exact
  * while app_max + 2*qmax <= 2047; a larger bound, or another lifting size, returns LDPC_EUNSUPPORTED.
  *
- * Every other combination (tanh-SP, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph with neither a compiled QC code nor
- * the IRA structure, quantized min-sum on IRA graphs, Z = 81, ldpc_decode_weighted, ldpc_decode_x0,
+ * LDPC_F_LAYERED with LDPC_ALGO_TANH_SP — layered tanh sum-product, fp32, per codeword (conventions of the flooding
+ * tanh-SP: L = -llr, the decision rule, the message cap = min(clamp, log 16777215), the fp32 module's p clamp):
+ *
+ *   APP_v = L_v for every v;  c2v[e] = 0 for every edge
+ *   for sweep in 0 .. iters-1:
+ *     for check c in ascending order:                                        (row-serial)
+ *       s_e    = APP_v(e) - c2v[e]                                  for each edge e of c
+ *       c2v[e] = sign * min(cap, log((1+|p|)/(1-|p|))),  p = prod_{e' != e} tanh(s_e'/2),
+ *                sign = xor of the sign bits of the other s_e'
+ *       APP_v(e) = s_e + c2v[e]
+ *     LDPC_F_EARLY_STOP: after the full sweep, stop the codeword when H * (z <= ZTHR) = 0; a stopped codeword is frozen
+ *   z_v = APP_v / 2;  bit_v = z_v <= ZTHR;  iters_used = sweeps run
+ *
+ * Defined by value, not bit for bit: the check rule is evaluated in the (D, S) form in log2 units, as every fp32
+ * tanh-SP kernel here, and held to 1e-5 * max(1, |z|) against the text above in float64
+ * (tests/test_gpu_layered_sp.py).  The plain form only: the reference has no layered schedule, so there is no
+ * golden whose exact zeros must be reproduced, and a codeword with exact-zero LLRs is decoded like any other — its
+ * messages may sit within 2^-23 (log2 units) of 0 where the ideal value is 0.  Implemented for the compiled
+ * 802.11n (1944,5/6) code (Z = 81) only; every other code returns LDPC_EUNSUPPORTED.
+ *
+ * Every other combination (tanh-SP on another code, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph with neither a compiled QC code nor
+ * the IRA structure, quantized min-sum on IRA graphs, min-sum at Z = 81, ldpc_decode_weighted, ldpc_decode_x0,
  * ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says which.  The flag is additive: ldpc_params and LDPC_ABI_VERSION are unchanged, and nothing changes while it is
  * clear.  The 802.11n forms need no kernel workspace. */
 

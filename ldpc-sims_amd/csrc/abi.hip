@@ -199,7 +199,7 @@ static int layered_check(const ldpc_graph* g, const ldpc_params* p) {
         why = "quantized min-sum on an IRA (DVB-S2) graph: the layered IRA kernel is float min-sum only";
     else if (g->ira && p->algo == LDPC_ALGO_MIN_SUM && !(p->flags & LDPC_F_F64) && ira_lay_why(g->ira))
         why = ira_lay_why(g->ira);
-    else if (p->algo == LDPC_ALGO_TANH_SP) why = "tanh sum-product: layered decoding is min-sum only";
+    else if (p->algo == LDPC_ALGO_TANH_SP) why = "tanh sum-product on this code: layered tanh-SP serves the 802.11n (1944,5/6) code only";
     else if (p->algo == LDPC_ALGO_QMIN_SUM && !qc_lay_pk_serves_z(qc_z(g->qc)))
         why = "quantized min-sum at this lifting size: the packed layered kernel serves 32 < Z <= 64";
     else if (p->algo == LDPC_ALGO_QMIN_SUM && !(p->flags & LDPC_F_F64) && !qc_lay_pk_exact(*p))

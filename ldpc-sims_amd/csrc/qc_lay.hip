@@ -280,8 +280,14 @@ bool qc_lay_pk_exact(const ldpc_params& p);
 int qc_launch_qms_lay_wifi1296_23(const void* llr, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
                                   int32_t* used, hipStream_t st);
 
+// layered tanh sum-product (qc_lay_sp.hip): the (1944,5/6) code, Z = 81, APP resident in LDS
+int qc_launch_sp_lay_wifi1944_56(const void* llr, int64_t B, const ldpc_params& p, uint8_t* bits, void* soft,
+                                 int32_t* used, hipStream_t st);
+
 bool qc_lay_supports(const QCSpec* s, const ldpc_params& p) {
-    if (!s || !lay_launcher(s) || (p.flags & LDPC_F_F64)) return false;
+    if (!s || (p.flags & LDPC_F_F64)) return false;
+    if (p.algo == LDPC_ALGO_TANH_SP) return qc_z(s) == Wifi1944_56::Z;
+    if (!lay_launcher(s)) return false;
     if (p.algo == LDPC_ALGO_QMIN_SUM) return qc_lay_pk_serves_z(qc_z(s)) && qc_lay_pk_exact(p);
     return p.algo == LDPC_ALGO_MIN_SUM;
 }
@@ -291,6 +297,7 @@ int qc_lay_decode(const QCSpec* s, const void* llr, int64_t B, const ldpc_params
     if (!qc_lay_supports(s, p)) return set_error(LDPC_EUNSUPPORTED, "no layered kernel for this code / algorithm");
     if (B <= 0) return LDPC_OK;
     if (p.algo == LDPC_ALGO_QMIN_SUM) return qc_launch_qms_lay_wifi1296_23(llr, B, p, bits, soft, iters_used, st);
+    if (p.algo == LDPC_ALGO_TANH_SP) return qc_launch_sp_lay_wifi1944_56(llr, B, p, bits, soft, iters_used, st);
     return lay_launcher(s)(llr, B, p, bits, soft, iters_used, st);
 }
 

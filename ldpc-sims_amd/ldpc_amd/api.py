@@ -167,7 +167,9 @@ class Decoder:
         ``include/ldpc_abi.h``): float min-sum on the 802.11n codes with Z <= 64, about half the iterations of
         flooding for the same error rate, and quantized min-sum (``algo="qms"``) on (1296,2/3) while
         ``app_max + 2*qmax <= 2047``; on IRA (DVB-S2) graphs float min-sum with one row of 360 checks per layer,
-        while the information bits fit a workgroup's LDS (DVB-S2 rate 1/2 does); anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
+        while the information bits fit a workgroup's LDS (DVB-S2 rate 1/2 does); tanh sum-product (``algo="tanh"``, fp32)
+        on the 802.11n (1944,5/6) code only: 25 sweeps measured 1.63x the codewords/s of 50 flooding iterations at a block
+        error rate no higher at any Eb/N0 point of the 16-QAM OFDM record (``profiles/layered/ab_sp.json``); anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
         is_torch = type(llr).__module__.startswith("torch")
         on_gpu = is_torch and llr.is_cuda
         fdt = np.float64 if precision == "f64" else np.float32

@@ -5,7 +5,9 @@ B = 65,536, LLRs generated on device at Eb/N0 0:0.5:5 dB, clamp 20 — or, with 
 --fixed-pair adds the same pair without early stop under "fixed_count"; or, with --code dvbs2_12, on config [4]'s:
 DVB-S2 rate 1/2, B = 4,096, Eb/N0 0:0.5:2 dB, the two-stream flooding IRA kernels at 50 iterations against the
 LDS-resident layered IRA kernel at 25 sweeps (its record also carries the slot count and the time per layer of one
-workgroup).  In one process on one GPU:
+workgroup); or, with --algo tanh --code wifi1944_56 --mod 16qam-ofdm, on config [2]'s: (1944,5/6) tanh sum-product,
+B = 32,768, 16-QAM OFDM LLRs at Eb/N0 4:0.5:9 dB, the flooding k_qc_sp_rs at 50 iterations against the LDS-resident
+layered k_qc_sp_lay at 25 sweeps.  In one process on one GPU:
 
   * block error rate of both legs at every Eb/N0 point (ldpc_count_errors), flooding at --flood-iters (50)
     and layered at --lay-iters (25);
@@ -18,6 +20,8 @@ workgroup).  In one process on one GPU:
         --fixed-pair --out profiles/layered/ab_q5.json
     python scripts/layered_ab.py --code dvbs2_12 --batch 4096 --ebn0 0:0.5:2 --pairs 10 --launches 5 --warmup 10 \
         --out profiles/layered/ab_ira.json
+    python scripts/layered_ab.py --algo tanh --code wifi1944_56 --mod 16qam-ofdm --batch 32768 --ebn0 4:0.5:9 \
+        --out profiles/layered/ab_sp.json
 
 Needs a GPU; writes one JSON record.
 """
@@ -40,7 +44,8 @@ def main():
     ap.add_argument("--ebn0", default="0:0.5:5")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--clamp", type=float, default=20.0)
-    ap.add_argument("--algo", default="minsum", choices=["minsum", "qms"])
+    ap.add_argument("--algo", default="minsum", choices=["minsum", "qms", "tanh"])
+    ap.add_argument("--mod", default="bpsk", choices=["bpsk", "16qam-ofdm"], help="LLR generator, as bench.py's --mod")
     ap.add_argument("--qstep", type=float, default=1.0, help="qms: LLR quantizer step (qmax 15, app_max 127)")
     ap.add_argument("--early-stop", action="store_true")
     ap.add_argument("--fixed-pair", action="store_true", help="with --early-stop: time the fixed-count pair too")
@@ -74,8 +79,16 @@ def main():
     llrs = []
     for i, e in enumerate(ebn0):  # bench.py's generation: same seeds, same points
         x = torch.empty((B, n), dtype=torch.float32, device="cuda")
-        sigma = float(np.sqrt(1.0 / (2.0 * (k / n) * 10.0 ** (e / 10.0))))
-        _abi.check(lib.ldpc_awgn_llr(cw.data_ptr(), x.data_ptr(), B, n, sigma, a.seed * 1000 + i, 0, st))
+        if a.mod == "bpsk":
+            sigma = float(np.sqrt(1.0 / (2.0 * (k / n) * 10.0 ** (e / 10.0))))
+            _abi.check(lib.ldpc_awgn_llr(cw.data_ptr(), x.data_ptr(), B, n, sigma, a.seed * 1000 + i, 0, st))
+        else:  # the OFDM front end, 32 subcarriers, 4 bits per symbol
+            from ldpc_amd.channel import ofdm_demod, ofdm_tx
+            esn0 = float(10.0 ** (e / 10.0) * (k / n) * 4)
+            s_ = cw.view(-1)
+            if (-s_.numel()) % 128:
+                s_ = torch.cat([s_, torch.zeros((-s_.numel()) % 128, dtype=torch.uint8, device="cuda")])
+            x.copy_(ofdm_demod(ofdm_tx(s_, 32, 4, esn0, a.seed * 1000 + i, 0), 32, 4, esn0)[:B * n].view(B, n))
         llrs.append(x)
     bits = torch.empty((B, n), dtype=torch.uint8, device="cuda")
 
@@ -119,7 +132,7 @@ def main():
             f, l = f0.elapsed_time(f1) / a.launches, l0.elapsed_time(l1) / a.launches
             pairs.append(dict(flooding_ms=f, layered_ms=l, layered_over_flooding_cw_per_s=f / l))
         ratios = [q["layered_over_flooding_cw_per_s"] for q in pairs]
-        out = dict(code=a.code, algo=a.algo, early_stop=early_stop, qstep=a.qstep, batch=B, ebn0_db=ebn0.tolist(), seed=a.seed, clamp=a.clamp, launches_per_leg=a.launches,
+        out = dict(code=a.code, algo=a.algo, mod=a.mod, early_stop=early_stop, qstep=a.qstep, batch=B, ebn0_db=ebn0.tolist(), seed=a.seed, clamp=a.clamp, launches_per_leg=a.launches,
                    library=_abi.library_digest(), device=torch.cuda.get_device_name(0),
                    legs={nm: dict(iters=lg["iters"], kernel_path=lg["kernel_path"], **bler[nm]) for nm, lg in legs.items()},
                    pairs=pairs, clock=sampler.summary())
