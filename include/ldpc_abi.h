@@ -66,6 +66,15 @@ enum {
  * codes with Z <= 64, LDPC_ALGO_MIN_SUM, fp32, through ldpc_decode_ex / ldpc_decode (host or device
  * pointers).
  *
+ * The same text, unchanged, on any other quasi-cyclic graph: when ldpc_graph_create finds that H is the lifting of a
+ * base matrix with one circulant per block (lifting sizes: the divisors of gcd(m, n) in [4, 1024], largest first) and
+ * no compiled table or IRA structure matched, a table-driven kernel reads shifts, columns and row degrees from a device
+ * table (kernel path "qct-z<Z>-layered").  LDPC_ALGO_MIN_SUM, fp32, base row degrees 2..27, and a codeword's
+ * 4 (n + Z) + 12 m bytes must fit the 160 KiB of LDS of a workgroup; otherwise LDPC_EUNSUPPORTED, naming the reason.
+ * No workspace.  Flooding, tanh-SP, quantized min-sum and fp64 on such graphs run on the generic kernels as before.
+ * Known gap: a graph that matches a compiled table is never offered to this kernel, so layered min-sum on the
+ * compiled (1944,5/6) code (Z = 81) still returns LDPC_EUNSUPPORTED.
+ *
  * LDPC_F_LAYERED on an IRA (DVB-S2-structured) graph — the same conventions, but a layer is one ROW of checks: with
  * m = 360 q checks, check c = a + q b is (row a, position b), and the 360 checks of a row are parallel:
  *
@@ -129,8 +138,8 @@ enum {
  * messages may sit within 2^-23 (log2 units) of 0 where the ideal value is 0.  Implemented for the compiled
  * 802.11n (1944,5/6) code (Z = 81) only; every other code returns LDPC_EUNSUPPORTED.
  *
- * Every other combination (tanh-SP on another code, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph with neither a compiled QC code nor
- * the IRA structure, quantized min-sum on IRA graphs, min-sum at Z = 81, ldpc_decode_weighted, ldpc_decode_x0,
+ * Every other combination (tanh-SP on another code, LDPC_F_F64, LDPC_F_FORCE_GENERIC, a graph with neither quasi-cyclic nor
+ * IRA structure, quantized min-sum on IRA graphs or on liftings without a compiled table, min-sum on the compiled Z = 81 code, ldpc_decode_weighted, ldpc_decode_x0,
  * ldpc_decode_bits_host) returns LDPC_EUNSUPPORTED and says which.  The flag is additive: ldpc_params and LDPC_ABI_VERSION are unchanged, and nothing changes while it is
  * clear.  The 802.11n forms need no kernel workspace. */
 
@@ -169,7 +178,8 @@ int ldpc_graph_info(const ldpc_graph* g, int32_t* m, int32_t* n, int32_t* nnz, i
 
 /* The kernel family a decode with these params runs on this graph: "qc-z<Z>" (register-resident
  * quasi-cyclic kernels, 802.11n), "qc-z<Z>-layered" (the same codes with LDPC_F_LAYERED), "ira-z360" (DVB-S2-structured IRA codes, min-sum, fixed count or early
- * stop), "ira-z360-layered" (the same graphs with LDPC_F_LAYERED) or
+ * stop), "ira-z360-layered" (the same graphs with LDPC_F_LAYERED), "qct-z<Z>-layered" (LDPC_F_LAYERED min-sum on a
+ * quasi-cyclic graph without a compiled table, Z the lifting size found) or
  * "generic-csr" (any H).  Introspection only (benchmarks label their records with it); NULL on bad
  * arguments.  The string is thread-local and valid until the next call on this thread.  No reference
  * counterpart: the reference has one code path (dense masks, bp/masking.py). */

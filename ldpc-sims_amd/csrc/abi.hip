@@ -26,6 +26,7 @@ struct ldpc_graph {
     int64_t W = 0;
     const ldpc::QCSpec* qc = nullptr;
     ldpc::IRASpec* ira = nullptr;  // DVB-S2-structured IRA code (ira.hip), when not QC
+    ldpc::QCTSpec* tab = nullptr;  // any other lifting with one circulant per block (qc_lay_tab.hip): layered min-sum
     std::mutex mtx;  // guards the internal workspace
     void* ws = nullptr;
     size_t ws_bytes = 0;
@@ -187,14 +188,23 @@ static bool use_lay(const ldpc_graph* g, const ldpc_params* p) {
 static bool use_ira_lay(const ldpc_graph* g, const ldpc_params* p) {
     return (p->flags & LDPC_F_LAYERED) && g->ira && !(p->flags & LDPC_F_FORCE_GENERIC) && ira_lay_supports(g->ira, *p);
 }
+// the same on a lifting without a compiled table: the table-driven kernel (qc_lay_tab.hip) or nothing
+static bool use_lay_tab(const ldpc_graph* g, const ldpc_params* p) {
+    return (p->flags & LDPC_F_LAYERED) && g->tab && !(p->flags & LDPC_F_FORCE_GENERIC) && qct_supports(g->tab, *p);
+}
 // LDPC_OK unless p asks for the layered schedule where it does not exist; the message names what is missing
 static int layered_check(const ldpc_graph* g, const ldpc_params* p) {
-    if (!(p->flags & LDPC_F_LAYERED) || use_lay(g, p) || use_ira_lay(g, p)) return LDPC_OK;
+    if (!(p->flags & LDPC_F_LAYERED) || use_lay(g, p) || use_ira_lay(g, p) || use_lay_tab(g, p)) return LDPC_OK;
     const char* why = "the code's lifting size: the layered kernel serves Z <= 64";
     if (p->flags & LDPC_F_FORCE_GENERIC) why = "LDPC_F_FORCE_GENERIC: the generic CSR kernels run the flooding schedule only";
-    else if (!g->qc && !g->ira)
-        why = "a graph without a compiled QC code or the IRA (DVB-S2) structure: layered decoding needs 802.11n "
-              "(648,1/2) or (1296,2/3), or an IRA graph";
+    else if (g->tab && p->algo == LDPC_ALGO_MIN_SUM && !(p->flags & LDPC_F_F64) && qct_why(g->tab))
+        why = qct_why(g->tab);
+    else if (g->tab && p->algo != LDPC_ALGO_MIN_SUM)
+        why = "tanh sum-product or quantized min-sum on a quasi-cyclic graph without a compiled table: the table-driven "
+              "layered kernel is float min-sum only";
+    else if (!g->qc && !g->ira && !g->tab)
+        why = "a graph without quasi-cyclic or IRA (DVB-S2) structure: layered decoding needs the lifting of a base "
+              "matrix with one circulant per block, or an IRA graph";
     else if (g->ira && p->algo == LDPC_ALGO_QMIN_SUM)
         why = "quantized min-sum on an IRA (DVB-S2) graph: the layered IRA kernel is float min-sum only";
     else if (g->ira && p->algo == LDPC_ALGO_MIN_SUM && !(p->flags & LDPC_F_F64) && ira_lay_why(g->ira))
@@ -216,7 +226,7 @@ static size_t elem_size(const ldpc_params* p) { return (p->flags & LDPC_F_F64) ?
 
 // Workspace = kernel scratch followed (host-pointer callers only) by staging for llr/bits/soft/used.
 static size_t kernel_ws(const ldpc_graph* g, int64_t B, const ldpc_params* p) {
-    if (use_lay(g, p)) return 0;
+    if (use_lay(g, p) || use_lay_tab(g, p)) return 0;
     if (use_ira_lay(g, p)) return align256(ira_lay_workspace(g->ira, B, *p));
     if (use_qc(g, p)) return align256(qc_workspace(g->qc, B, *p));
     if (use_ira(g, p)) return align256(ira_workspace(g->ira, B, *p));
@@ -268,35 +278,59 @@ static int build_graph(ldpc_graph* g, int m, int n, const std::vector<int32_t>& 
     return LDPC_OK;
 }
 
+// Is H the lifting by z of a base matrix with at most one circulant per block?  rows[r] receives base row r's (block
+// column, shift) pairs in ascending column.  Check 0 of a base row defines its blocks and every other check of the
+// row is held to them; the first check that disagrees ends the search (no dense base matrix is formed).
+using BaseRows = std::vector<std::vector<std::pair<int, int>>>;
+static bool qc_blocks(int m, int n, int z, const std::vector<int32_t>& row_ptr, const std::vector<int32_t>& col_idx,
+                      BaseRows& rows) {
+    if (m % z || n % z) return false;
+    const int mb = m / z;
+    rows.assign(mb, {});
+    for (int r = 0; r < mb; ++r) {
+        auto& row = rows[r];
+        for (int e = row_ptr[r * z]; e < row_ptr[r * z + 1]; ++e) {
+            const int j = col_idx[e] / z;
+            if (!row.empty() && row.back().first == j) return false;  // two entries in one block
+            row.push_back({j, col_idx[e] % z});
+        }
+        for (int i = 1; i < z; ++i) {
+            const int c = r * z + i;
+            if (row_ptr[c + 1] - row_ptr[c] != (int)row.size()) return false;
+            int e = row_ptr[c];
+            for (const auto& b : row)
+                if (col_idx[e++] != b.first * z + (i + b.second) % z) return false;
+        }
+    }
+    return true;
+}
+
 // Recognise H as the lifting of a base matrix with a compiled QC kernel.
 static const QCSpec* detect_qc(int m, int n, const std::vector<int32_t>& row_ptr, const std::vector<int32_t>& col_idx) {
     static const int zs[] = {27, 54, 81, 96, 360};
+    BaseRows rows;
     for (int z : zs) {
-        if (m % z || n % z) continue;
+        if (!qc_blocks(m, n, z, row_ptr, col_idx, rows)) continue;
         const int mb = m / z, nb = n / z;
         std::vector<int32_t> sh((size_t)mb * nb, -1);
-        bool ok = true;
-        // row r*z+0 of each block row defines the shifts; verify every row of every block.
-        for (int r = 0; r < mb && ok; ++r)
-            for (int e = row_ptr[r * z]; e < row_ptr[r * z + 1]; ++e) {
-                const int j = col_idx[e] / z;
-                sh[(size_t)r * nb + j] = col_idx[e] % z;
-            }
-        for (int r = 0; r < mb && ok; ++r)
-            for (int i = 0; i < z && ok; ++i) {
-                const int c = r * z + i;
-                int cnt = 0;
-                for (int j = 0; j < nb; ++j) cnt += sh[(size_t)r * nb + j] >= 0;
-                if (row_ptr[c + 1] - row_ptr[c] != cnt) { ok = false; break; }
-                int e = row_ptr[c];
-                for (int j = 0; j < nb; ++j) {
-                    const int s = sh[(size_t)r * nb + j];
-                    if (s < 0) continue;
-                    if (col_idx[e++] != j * z + (i + s) % z) { ok = false; break; }
-                }
-            }
-        if (!ok) continue;
+        for (int r = 0; r < mb; ++r)
+            for (const auto& b : rows[r]) sh[(size_t)r * nb + b.first] = b.second;
         if (const QCSpec* spec = qc_lookup(mb, nb, z, sh.data())) return spec;
+    }
+    return nullptr;
+}
+
+// Any other lifting: the divisors of gcd(m, n) in [4, 1024], largest first (the smallest base matrix); its table goes
+// to the device once.  Null when H is no lifting (or the upload failed: the graph then has the generic paths only).
+static QCTSpec* detect_lifting(int m, int n, const std::vector<int32_t>& row_ptr, const std::vector<int32_t>& col_idx,
+                               int device) {
+    int g = m, b = n;
+    while (b) { const int t = g % b; g = b; b = t; }
+    BaseRows rows;
+    for (int z = std::min(g, 1024); z >= 4; --z) {
+        if (g % z || !qc_blocks(m, n, z, row_ptr, col_idx, rows)) continue;
+        DeviceGuard dg(device);
+        return qct_create(m / z, n / z, z, rows, device);
     }
     return nullptr;
 }
@@ -381,6 +415,7 @@ int ldpc_graph_create(int32_t m, int32_t n, int32_t nnz, const int32_t* row_ptr,
     }
     g->qc = detect_qc(m, n, rp, ci);
     if (!g->qc) g->ira = ira_detect(m, n, rp.data(), ci.data(), device);
+    if (!g->qc && !g->ira) g->tab = detect_lifting(m, n, rp, ci, device);
     *out = g;
     return LDPC_OK;
 }
@@ -410,6 +445,7 @@ int ldpc_graph_destroy(ldpc_graph* g) {
     (void)hipFree(g->d_var_edges);
     (void)hipFree(g->d_wofs);
     ira_free(g->ira);
+    qct_free(g->tab);
     if (g->ws) (void)hipFree(g->ws);
     pipe_free(g);
     delete g;
@@ -434,6 +470,7 @@ const char* ldpc_kernel_path(const ldpc_graph* g, const ldpc_params* p) {
     if (layered_check(g, p) != LDPC_OK) return nullptr;
     if (use_lay(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc)) + "-layered";
     else if (use_ira_lay(g, p)) path = "ira-z360-layered";
+    else if (use_lay_tab(g, p)) path = "qct-z" + std::to_string(qct_z(g->tab)) + "-layered";
     else if (use_qc(g, p)) path = "qc-z" + std::to_string(qc_z(g->qc));
     else if (use_ira(g, p)) path = "ira-z360";
     else path = "generic-csr";
@@ -505,6 +542,8 @@ static int decode_impl(const ldpc_graph* gc, const void* llr, int64_t B, const l
         rc = qc_lay_decode(g->qc, llr_d, B, *p, bits_d, soft_d, used_d, st);
     } else if (use_ira_lay(g, p)) {
         rc = ira_lay_decode(g->ira, (const float*)llr_d, B, *p, bits_d, (float*)soft_d, used_d, ws, st);
+    } else if (use_lay_tab(g, p)) {
+        rc = qct_decode(g->tab, (const float*)llr_d, B, *p, bits_d, (float*)soft_d, used_d, st);
     } else if (use_qc(g, p)) {
         rc = qc_decode(g->qc, llr_d, B, *p, bits_d, soft_d, used_d, ws, st);
     } else if (use_ira(g, p) && !w) {

@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "ldpc_abi.h"
 
@@ -532,4 +534,19 @@ const char* ira_lay_why(const IRASpec* s);
 size_t ira_lay_workspace(const IRASpec* s, int64_t B, const ldpc_params& p);
 int ira_lay_decode(const IRASpec* s, const float* llr, int64_t B, const ldpc_params& p, uint8_t* bits, float* soft,
                    int32_t* iters_used, char* ws, hipStream_t st);
+}  // namespace ldpc
+
+// Table-driven layered min-sum for any lifting with one circulant per block and no compiled table (qc_lay_tab.hip,
+// LDPC_F_LAYERED): rows[r] lists base row r's (block column, shift) pairs in ascending column; the table is uploaded
+// once (the caller has set the device).  fp32 min-sum while row degrees are 2..27 and a codeword's posteriors and check
+// states fit a workgroup's LDS; qct_why names what rules a graph out (null: nothing).  No workspace.
+namespace ldpc {
+struct QCTSpec;
+QCTSpec* qct_create(int mb, int nb, int z, const std::vector<std::vector<std::pair<int, int>>>& rows, int device);
+void qct_free(QCTSpec* s);
+int qct_z(const QCTSpec* s);
+bool qct_supports(const QCTSpec* s, const ldpc_params& p);
+const char* qct_why(const QCTSpec* s);
+int qct_decode(const QCTSpec* s, const float* llr, int64_t B, const ldpc_params& p, uint8_t* bits, float* soft,
+               int32_t* iters_used, hipStream_t st);
 }  // namespace ldpc

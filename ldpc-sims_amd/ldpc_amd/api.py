@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import Params, check
-from .codes import Graph, SparseCode
+from .codes import Graph, QCCode, SparseCode
 
 _ALGOS = {"tanh": _abi.ALGO_TANH_SP, "sp": _abi.ALGO_TANH_SP, "tanh_sp": _abi.ALGO_TANH_SP,
           "minsum": _abi.ALGO_MIN_SUM, "min_sum": _abi.ALGO_MIN_SUM, "ms": _abi.ALGO_MIN_SUM,
@@ -40,7 +40,12 @@ class Decoder:
 
     def __init__(self, H, device: int = 0):
         self.lib = _abi.load()
-        g = Graph.from_H(H if isinstance(H, (SparseCode, Graph)) else np.asarray(H)) if not isinstance(H, Graph) else H
+        if isinstance(H, Graph):
+            g = H
+        elif isinstance(H, QCCode):   # straight from the base matrix: no dense H
+            g = Graph.from_qc(H.base, H.Z)
+        else:
+            g = Graph.from_H(H if isinstance(H, SparseCode) else np.asarray(H))
         self.m, self.n, self.E = g.m, g.n, g.E
         self.device = int(device)
         h = ctypes.c_void_p()
@@ -87,7 +92,8 @@ class Decoder:
 
     def kernel_path(self, p: Params) -> str:
         """The kernel family a decode with these params runs: "qc-z<Z>", "qc-z<Z>-layered", "ira-z360",
-        "ira-z360-layered" or "generic-csr"."""
+        "ira-z360-layered", "qct-z<Z>-layered" (layered min-sum on a quasi-cyclic graph without a compiled table,
+        Z the lifting size found) or "generic-csr"."""
         s = self.lib.ldpc_kernel_path(self._h, ctypes.byref(p))
         if s is None:
             raise _abi.LdpcError(_abi.LDPC_EINVAL, self.lib.ldpc_last_error().decode(errors="replace"))
@@ -169,7 +175,12 @@ class Decoder:
         ``app_max + 2*qmax <= 2047``; on IRA (DVB-S2) graphs float min-sum with one row of 360 checks per layer,
         while the information bits fit a workgroup's LDS (DVB-S2 rate 1/2 does); tanh sum-product (``algo="tanh"``, fp32)
         on the 802.11n (1944,5/6) code only: 25 sweeps measured 1.63x the codewords/s of 50 flooding iterations at a block
-        error rate no higher at any Eb/N0 point of the 16-QAM OFDM record (``profiles/layered/ab_sp.json``); anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
+        error rate no higher at any Eb/N0 point of the 16-QAM OFDM record (``profiles/layered/ab_sp.json``); float
+        min-sum on any other quasi-cyclic graph — the lifting of a base matrix with one circulant per block, however
+        it arrives (dense H, ``Graph.from_qc``, a ``QCCode``) — through a table-driven kernel, while base row degrees
+        are 2..27 and a codeword fits a workgroup's LDS (``4 (n + Z) + 12 m`` bytes of 160 KiB); flooding, tanh, qms
+        and fp64 on such graphs stay on the generic kernels.  Known gap: min-sum on the compiled (1944,5/6) code has
+        no layered kernel.  Anything else raises ``LdpcError`` (``LDPC_EUNSUPPORTED``)."""
         is_torch = type(llr).__module__.startswith("torch")
         on_gpu = is_torch and llr.is_cuda
         fdt = np.float64 if precision == "f64" else np.float32
@@ -351,9 +362,14 @@ _cache_lock = threading.Lock()
 
 def get_decoder(H, device: int = 0) -> Decoder:
     """Graphs are built once per (H, device) — the reference rebuilt its dense masks on every
-    decode_bits call (ofdm_functions.py:143/145)."""
-    if isinstance(H, SparseCode):
-        key = (H.shape, hashlib.sha1(H.row_ptr.tobytes() + H.col_idx.tobytes()).hexdigest(), int(device))
+    decode_bits call (ofdm_functions.py:143/145).  ``H``: a dense 0/1 matrix, a ``SparseCode``, a ``Graph`` or a
+    ``QCCode`` (keyed on its base matrix and Z; the graph is built from the base matrix, without a dense H)."""
+    if isinstance(H, QCCode):
+        base = np.ascontiguousarray(H.base, np.int32)
+        key = ("qc", base.shape, int(H.Z), hashlib.sha1(base.tobytes()).hexdigest(), int(device))
+    elif isinstance(H, (SparseCode, Graph)):
+        key = ((H.m, H.n), hashlib.sha1(np.asarray(H.row_ptr, np.int32).tobytes()
+                                       + np.asarray(H.col_idx, np.int32).tobytes()).hexdigest(), int(device))
     else:
         H = np.asarray(H)
         key = (H.shape, hashlib.sha1(np.packbits(H.astype(np.uint8) & 1).tobytes()).hexdigest(), int(device))

@@ -220,6 +220,24 @@ class Graph:
         var_ptr = np.cumsum(var_ptr).astype(np.int32)
         return cls(m, n, row_ptr, col_idx, var_ptr, order, rows.astype(np.int32))
 
+    @classmethod
+    def from_qc(cls, base, Z: int) -> "Graph":
+        """The graph of ``qc_expand(base, Z)`` built straight from the base matrix (``-1`` = null block), without
+        the dense H: check ``r*Z + i`` has one edge per block of base row r, to variable ``j*Z + (i + shift) mod Z``,
+        in ascending block column (ascending variable, as ``from_H``)."""
+        base = np.asarray(base, np.int64)
+        if base.ndim != 2 or Z < 1 or base.min() < -1 or base.max() >= Z:
+            raise ValueError("base must be a 2-D matrix of shifts in [-1, Z)")
+        mb, nb = base.shape
+        i = np.arange(Z)[:, None]
+        cols = []
+        for r in range(mb):
+            j = np.nonzero(base[r] >= 0)[0]
+            cols.append((j * Z + (i + base[r, j]) % Z).ravel())   # (Z, d) row-major: check by check
+        deg = np.repeat((base >= 0).sum(axis=1), Z)
+        row_ptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+        return cls.from_csr(mb * Z, nb * Z, row_ptr, np.concatenate(cols).astype(np.int32))
+
     def check_degrees(self) -> np.ndarray:
         return np.diff(self.row_ptr)
 

@@ -2,7 +2,8 @@
 """Per-kernel register / spill / scratch figures of a built library, read from the gfx950 code objects'
 AMDGPU metadata notes (no GPU needed).
 
-    python scripts/kernel_resources.py [LIB.so] [--filter SUBSTR]
+    python scripts/kernel_resources.py [LIB.so] [--filter=SUBSTR]
+    python scripts/kernel_resources.py --filter=lay_tab     # the 24 k_qc_ms_lay_tab<DMAX, EARLY, NORM>
 
 libldpc_hip.so's .hip_fatbin section holds one clang offload bundle per compiled source; each bundle's
 gfx950 entry is an ELF code object whose NT_AMDGPU_METADATA note lists, per kernel, .vgpr_count,

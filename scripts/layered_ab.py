@@ -7,7 +7,9 @@ DVB-S2 rate 1/2, B = 4,096, Eb/N0 0:0.5:2 dB, the two-stream flooding IRA kernel
 LDS-resident layered IRA kernel at 25 sweeps (its record also carries the slot count and the time per layer of one
 workgroup); or, with --algo tanh --code wifi1944_56 --mod 16qam-ofdm, on config [2]'s: (1944,5/6) tanh sum-product,
 B = 32,768, 16-QAM OFDM LLRs at Eb/N0 4:0.5:9 dB, the flooding k_qc_sp_rs at 50 iterations against the LDS-resident
-layered k_qc_sp_lay at 25 sweeps.  In one process on one GPU:
+layered k_qc_sp_lay at 25 sweeps; or, with --code qc:MBxNBxZ[:SEED], on a seeded random quasi-cyclic code (column
+weight 3 information part, staircase parity part) that has no compiled table: flooding on the generic CSR kernels
+against the table-driven layered k_qc_ms_lay_tab.  In one process on one GPU:
 
   * block error rate of both legs at every Eb/N0 point (ldpc_count_errors), flooding at --flood-iters (50)
     and layered at --lay-iters (25);
@@ -22,6 +24,8 @@ layered k_qc_sp_lay at 25 sweeps.  In one process on one GPU:
         --out profiles/layered/ab_ira.json
     python scripts/layered_ab.py --algo tanh --code wifi1944_56 --mod 16qam-ofdm --batch 32768 --ebn0 4:0.5:9 \
         --out profiles/layered/ab_sp.json
+    python scripts/layered_ab.py --code qc:12x24x81 --batch 16384 --ebn0 1:0.5:3.5 --pairs 8 --launches 6 --warmup 12 \
+        --out profiles/layered/ab_tab.json
 
 Needs a GPU; writes one JSON record.
 """
@@ -35,6 +39,21 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ldpc-sims_amd"))
+
+
+def qc_random_base(mb, nb, Z, seed, dv=3):
+    """Base matrix of a random QC code: dv shifts per information column, a staircase (dual-diagonal) parity part."""
+    rng = np.random.default_rng(seed)
+    base = -np.ones((mb, nb), np.int32)
+    kb = nb - mb
+    for j in range(kb):
+        rows = rng.choice(mb, size=min(dv, mb), replace=False)
+        base[rows, j] = rng.integers(0, Z, size=len(rows))
+    for r in range(mb):
+        base[r, kb + r] = 0
+        if r + 1 < mb:
+            base[r + 1, kb + r] = 0
+    return base
 
 
 def main():
@@ -65,10 +84,19 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("layered_ab.py measures on a GPU; none is visible")
     lib = _abi.load()
-    H, _ = ldpc_amd.get_code(a.code)
+    base = None
+    if a.code.startswith("qc:"):
+        dims, *rest = a.code[3:].split(":")
+        mb, nb, Z = (int(v) for v in dims.split("x"))
+        base = qc_random_base(mb, nb, Z, int(rest[0]) if rest else 5)
+        qc = ldpc_amd.codes.QCCode(base, Z, name=a.code)
+        H = qc.H()
+        dec = ldpc_amd.get_decoder(qc, 0)
+    else:
+        H, _ = ldpc_amd.get_code(a.code)
+        dec = ldpc_amd.get_decoder(H, 0)
     m, n = H.shape
     k, B = n - m, a.batch
-    dec = ldpc_amd.get_decoder(H, 0)
     stream = torch.cuda.current_stream()
     st = stream.cuda_stream
     lo, step, hi = (float(x) for x in a.ebn0.split(":"))
@@ -148,6 +176,8 @@ def main():
             trips = -(-B // slots)
             out["legs"]["layered"].update(slots=slots, codewords_per_slot=trips, us_per_layer=out["legs"]["layered"][
                 "launch_ms_median"] * 1e3 / (trips * lay["iters"] * (m // 360)))
+        if base is not None:
+            out["base_matrix"] = dict(Z=Z, shifts=base.tolist())
         out["ratio_median"] = statistics.median(ratios)
         out["ratio_min"], out["ratio_max"] = min(ratios), max(ratios)
         return out, legs
